@@ -9,19 +9,33 @@ past its end); the separately allocated layout is timed too and reported as `oth
 (separate 1 GiB allocations land in one of two physical placement modes).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mib 1024] [--dtype float32] [--op sum]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it fills the operands, warms up, times the K steps, writes
+the outputs when --dump-outputs is given, and prints the line.  Every other leg listed below (marked
+--full) takes runs of its own and is measured only with --full.
+
+--dump-outputs DIR writes what the timed path left its caller after the last timed step, the combined
+`recv` operand (warmup + steps applications of the op), as DIR/recv.npy (DIR/recv_rank<r>.npy at N > 1):
+float32 for the floating dtypes up to fp32, float64 otherwise; an operand above DUMP_ALL_ELEMS elements is
+sampled (dump_slices: both ends and seeded random blocks, the same for every run with the same arguments).
+The operands are counter-based (seed 0xDCC1), so two builds run with the same arguments combine the same
+inputs and their dumps compare element for element.
 
 Rank 0 prints ONE JSON line:
   value            whole-job HBM traffic rate, GiB/s = N * 3 * bytes_per_operand / t_step
                    (3 = read send + read recv + write recv; BASELINE.md §2 roofline basis)
+  ms_per_step      milliseconds one timed step took (wall time of the timed region / steps, max over ranks)
   roofline         dominant kernel (the combine): algorithmic bytes per launch / average
                    launch duration (HIP events around the timed region on the launch stream,
                    divided by the steps), vs 8.0 TB/s HBM peak;
-                   `traffic` = HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
+                   `traffic` (--full) = HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
                    run during the bench (N=1) over the same kernel and layout (measured_traffic)
-  cpu_baseline     the build's C restatement of the reference loop (oracle/host_reduce.c, Release flags)
+  cpu_baseline     (--full) the build's C restatement of the reference loop (oracle/host_reduce.c, Release flags)
                    on the headline's own 1 GiB operands in host memory: 1 core and every core this
                    process may use (rank 0, N=1); nproc and the CPU model are stated
-Extra keys: c3 (BASELINE C3: 4 ops x fp16/bf16/fp32/int32/int64 at 1 GiB, timed and sample-verified) and
+  verified         (--full) the timed combines' result, sampled and checked against plain torch ops (verify_sample)
+Extra keys, all --full: c3 (BASELINE C3: 4 ops x fp16/bf16/fp32/int32/int64 at 1 GiB, timed and sample-verified) and
 c4 (BASELINE C4: fp32 Sum size sweep 4 KiB - 4 GiB, 21 points, operand sets rotated below a 512 MiB working
 set, per-launch duration eager from Python and from a C++ loop, and graph-replayed, fraction of HBM peak), rank 0 at N=1; payload_gib_s, host_staged (H2D+combine+D2H rate for host-resident operands,
 rank 0, N=1), allgather (RCCL all-gather of the shards over xGMI, N>1, reported separately),
@@ -95,7 +109,7 @@ def parse(argv=None):
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-host-staged", action="store_true")
     p.add_argument("--c5-gib", type=float, default=16.0,
-                   help="BASELINE C5 extra on every run: one buffer of this many GiB per operand sharded over "
+                   help="BASELINE C5 extra of every --full run: one buffer of this many GiB per operand sharded over "
                         "the N GPUs, combine + RCCL all-gather, reported as `c5` (0 disables)")
     p.add_argument("--no-pmc", action="store_true",
                    help="skip the rocprofv3 --pmc passes that measure roofline.traffic (N=1)")
@@ -109,7 +123,18 @@ def parse(argv=None):
                    help="test aid: each rank joins a gloo group and rank 0 prints the world it saw (no GPU)")
     p.add_argument("--other-pairs", type=int, default=4,
                    help="separately allocated operand pairs timed for `other_layout` (median reported)")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline: the sampled check of the result, CPU baseline, "
+                        "PMC traffic, C3 / C4 / C5, ring step, other layout, host-resident operands, and at N > 1 "
+                        "the all-gather and the namespace-dccl collectives (the --no-* options prune them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the combined operand (sampled above DUMP_ALL_ELEMS elements) "
+                        "as DIR/recv.npy (DIR/recv_rank<r>.npy at N > 1)")
+    a = p.parse_args(argv)
+    if not a.full:  # a plain run: the headline alone, every other leg off
+        a.no_cpu = a.no_host_staged = a.no_pmc = a.no_other_layout = a.no_configs = True
+        a.c5_gib = 0.0
+    return a
 
 
 def synth_into(t: torch.Tensor, n: int, dt: int, op: int, buffer_id: int) -> None:
@@ -173,6 +198,43 @@ def verify_sample(recv: torch.Tensor, n: int, dt: int, op: int, send_id: int, re
         if got.view(torch.uint8).cpu().numpy().tobytes() != want.view(torch.uint8).cpu().numpy().tobytes():
             return False
     return True
+
+
+DUMP_ALL_ELEMS = 4 << 20   # an output of at most this many elements is dumped whole (16 MiB as float32)
+DUMP_EDGE_ELEMS = 1 << 20  # a larger one: this many elements from each end ...
+DUMP_BLOCKS = 64           # ... and this many seeded random blocks of DUMP_BLOCK_ELEMS between them (4 Mi elements
+DUMP_BLOCK_ELEMS = 1 << 15  # in all: 16 MiB as float32, 32 MiB as float64)
+NUMPY_DTYPES = {0: np.int8, 1: np.uint8, 2: np.int32, 3: np.uint32, 4: np.int64, 5: np.uint64, 6: np.float16,
+                7: np.float32, 8: np.float64, 9: np.uint16}  # bf16 travels as its 16 bits
+
+
+def dump_slices(n: int) -> list:
+    """[first, last) element ranges of an n-element output that --dump-outputs keeps, in order: everything up to
+    DUMP_ALL_ELEMS, else both ends and DUMP_BLOCKS random blocks drawn from a generator seeded with SEED and n
+    alone (the same ranges in every run of the same size)."""
+    if n <= DUMP_ALL_ELEMS:
+        return [(0, n)]
+    import random
+    rnd = random.Random(SEED ^ n)
+    span = n - 2 * DUMP_EDGE_ELEMS - DUMP_BLOCK_ELEMS
+    mids = sorted(DUMP_EDGE_ELEMS + rnd.randrange(0, span + 1) for _ in range(DUMP_BLOCKS))
+    return [(0, DUMP_EDGE_ELEMS), *((m, m + DUMP_BLOCK_ELEMS) for m in mids), (n - DUMP_EDGE_ELEMS, n)]
+
+
+def dump_outputs(outdir: str, recv: torch.Tensor, n: int, dt: int, name: str) -> str:
+    """--dump-outputs: write the ranges dump_slices(n) of the combined operand `recv` as outdir/<name>.npy, float32
+    for fp16 / bf16 / fp32 (exact), float64 for the other dtypes (exact but for 64-bit integers above 2^53)."""
+    esz = dccl_amd.size_of_type(dt)
+    raw = recv.view(torch.uint8)
+    parts = [raw[a0 * esz:a1 * esz].cpu().numpy().view(NUMPY_DTYPES[dt]) for a0, a1 in dump_slices(n)]
+    arr = np.concatenate(parts)
+    if dt == 9:
+        arr = (arr.astype(np.uint32) << 16).view(np.float32)
+    arr = arr.astype(np.float32 if dt in (6, 7, 9) else np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    path = os.path.join(outdir, name + ".npy")
+    np.save(path, arr)
+    return path
 
 
 def time_kernel(ps: int, pr: int, dt: int, n: int, op: int, stream, steps: int) -> float:
@@ -1399,15 +1461,18 @@ def run_rank(a):
         kern_ms_max = kern_ms
     ms_per_step = elapsed / a.steps * 1e3
     progress(f"timed region done: {ms_per_step:.4f} ms per step, kernel {kern_ms:.4f} ms")
+    if a.dump_outputs:
+        path = dump_outputs(a.dump_outputs, recv, n, dt, "recv" if world == 1 else f"recv_rank{rank}")
+        progress(f"outputs written: {path}")
     # the timed combines' result, sampled: warmup + steps applications of the op on this rank's operands
-    ok = verify_sample(recv, n, dt, op, 2 * rank, 2 * rank + 1, a.warmup + a.steps)
-    if world > 1:
+    ok = verify_sample(recv, n, dt, op, 2 * rank, 2 * rank + 1, a.warmup + a.steps) if a.full else None
+    if world > 1 and a.full:
         flag = torch.tensor([-1 if ok is None else int(ok)], dtype=torch.int32, device=coll_dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         ok = None if int(flag[0]) < 0 else bool(flag[0])
 
     extra = {}
-    if world > 1:  # the exchange step: RCCL all-gather of the reduced shards (reported separately)
+    if world > 1 and a.full:  # the exchange step: RCCL all-gather of the reduced shards (reported separately)
         width = max(b - a_ for a_, b in bounds) if strong else n
         src = recv if width == n else torch.cat([recv, recv.new_zeros(width - n)])
         src = src.to(coll_dev)
@@ -1448,7 +1513,7 @@ def run_rank(a):
         progress(f"other layout ({other}): median {extra['other_layout']['frac']:.4f} of peak")
     if a.c5_gib > 0 and not strong:
         extra["c5"] = c5_extra(a, world, rank, dev, backend, coll_dev)
-    if world > 1:
+    if world > 1 and a.full:
         # DCCL_BENCH_AR_TRANSPORTS=direct with the gloo backend rehearses the direct path with several
         # processes on one GPU (RCCL refuses two ranks on one device)
         rehearse = backend == "gloo" and os.environ.get("DCCL_BENCH_AR_TRANSPORTS") == "direct"
@@ -1515,7 +1580,8 @@ def run_rank(a):
             res["allgather"] = extra["allgather"]
         if "dccl_allreduce" in extra:
             res["dccl_allreduce"] = extra["dccl_allreduce"]
-        res["traffic_measurement"] = traffic_detail
+        if a.full:
+            res["traffic_measurement"] = traffic_detail
         res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                            "kernel": "reduce_vec_kernel (dccl_local_reduce)",
@@ -1529,7 +1595,8 @@ def run_rank(a):
                 res[key] = extra[key]
         if "dccl_allreduce" in extra:
             res["dccl_allreduce_summary"] = allreduce_summary(extra["dccl_allreduce"])
-        res["verified"] = ok
+        if a.full:
+            res["verified"] = ok
         print(json.dumps(res), flush=True)
     if world > 1:
         try:

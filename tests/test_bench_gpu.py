@@ -58,7 +58,7 @@ def test_bench_direct_allreduce_two_processes_one_gpu():
            "DCCL_BOOTSTRAP_TAG": f"bench_rehearsal_{_port()}"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--mib", "64", "--c5-gib", "0.25", "--no-cpu", "--no-host-staged"]
+           "--warmup", "1", "--mib", "64", "--c5-gib", "0.25", "--no-cpu", "--no-host-staged", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -86,7 +86,7 @@ def test_bench_self_launch_two_ranks_one_gpu():
     env.update({"DCCL_BENCH_BACKEND": "gloo", "DCCL_BENCH_AR_TRANSPORTS": "direct",
                 "DCCL_BOOTSTRAP_TAG": f"bench_self_launch_{_port()}"})
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--mib", "64",
-           "--c5-gib", "0.25", "--no-cpu", "--other-pairs", "2"]
+           "--c5-gib", "0.25", "--no-cpu", "--other-pairs", "2", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -117,7 +117,7 @@ def test_bench_rccl_two_ranks_one_gpu():
     env.update({"DCCL_BENCH_BACKEND": "nccl", "DCCL_BENCH_RCCL_REHEARSAL": "1",
                 "DCCL_BOOTSTRAP_TAG": f"bench_rccl_rehearsal_{_port()}"})
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--mib", "64",
-           "--c5-gib", "0.25", "--no-cpu", "--other-pairs", "2", "--rank-timeout", "240"]
+           "--c5-gib", "0.25", "--no-cpu", "--other-pairs", "2", "--rank-timeout", "240", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -169,14 +169,14 @@ def test_host_crossover_leg(monkeypatch):
 
 
 def test_bench_single_gpu_line():
-    """bench.py at N=1 prints exactly one JSON line with the contract's keys, the C5 extra and the C3 / C4
+    """bench.py --full at N=1 prints exactly one JSON line with the contract's keys, the C5 extra and the C3 / C4
     legs (every C3 entry sample-verified)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--mib", "64", "--c5-gib", "0.5",
-           "--no-host-staged", "--cpu-seconds", "1"]
+           "--no-host-staged", "--cpu-seconds", "1", "--full"]
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -202,3 +202,47 @@ def test_bench_single_gpu_line():
     granted = max(1, min(cb["affinity_cpus"], int(q))) if q else cb["affinity_cpus"]
     assert cb["all_cores"]["cores"] == granted  # the quota's CPUs, not a throttled thread per affinity CPU
     assert (cb["affinity_threads"] is None) == (cb["affinity_cpus"] <= granted)
+
+
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain run (no --full) prints the headline's keys and runs no leg beside the timed steps, and
+    --dump-outputs writes the combined operand: at 64 MiB the sampled ranges of bench.dump_slices, as float32,
+    bit for bit what the oracle gives for warmup + steps applications of the op on the same synthetic inputs."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import bench
+    import oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--mib", "64",
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-3000:]
+    res = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in res, key
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["dtype"] == "f32" and res["higher_is_better"] is True
+    assert res["ms_per_step"] > 0 and res["value"] > 0 and res["roofline"]["traffic"] is None
+    for key in ("cpu_baseline", "c3", "c4", "c5", "other_layout", "ring_step", "host_staged", "host_crossover",
+                "traffic_measurement", "verified"):
+        assert key not in res, key
+    assert [f.name for f in out.iterdir()] == ["recv.npy"]
+    got = np.load(out / "recv.npy")
+    n = (64 << 20) // 4
+    slices = bench.dump_slices(n)
+    assert got.dtype == np.float32 and got.size == sum(b - a for a, b in slices) < n
+    at = 0
+    for a, b in slices:
+        s = oracle.synth(b - a, 7, 0, bench.SEED, 0, first=a)
+        want = oracle.synth(b - a, 7, 0, bench.SEED, 1, first=a)
+        for _ in range(4):  # warmup + steps
+            want = oracle.combine(s, want, 7, 0)
+        assert got[at:at + b - a].tobytes() == want.tobytes(), (a, b)
+        at += b - a

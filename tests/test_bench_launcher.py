@@ -102,3 +102,28 @@ def test_socket_rehearsal_sizes_only_when_ranks_share_gpus(monkeypatch):
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
     assert not bench.socket_rehearsal(8, "nccl")
     assert bench.REHEARSAL_CHILD_TIMEOUT_S > bench.CHILD_TIMEOUT_S and bench.REHEARSAL_AR_MIB < 256
+
+
+def test_plain_run_switches_every_other_leg_off():
+    """Without --full the parsed options leave only the headline; with it they are the user's own."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert a.no_cpu and a.no_host_staged and a.no_pmc and a.no_other_layout and a.no_configs and a.c5_gib == 0
+    a = bench.parse(["--full", "--no-pmc", "--dump-outputs", "d"])
+    assert a.full and a.no_pmc and a.dump_outputs == "d" and a.c5_gib == 16.0
+    assert not (a.no_cpu or a.no_host_staged or a.no_other_layout or a.no_configs)
+
+
+def test_dump_slices_are_fixed_and_bounded():
+    """--dump-outputs keeps a small output whole and a fixed sample of a large one: ordered ranges inside the
+    output, both ends among them, the same on every call, at most 64 MB as float64."""
+    import bench
+    assert bench.dump_slices(5) == [(0, 5)]
+    assert bench.dump_slices(bench.DUMP_ALL_ELEMS) == [(0, bench.DUMP_ALL_ELEMS)]
+    for n in (bench.DUMP_ALL_ELEMS + 1, (1 << 28) + 3, 1 << 33):
+        s = bench.dump_slices(n)
+        assert s == bench.dump_slices(n) and s == sorted(s)
+        assert s[0][0] == 0 and s[-1][1] == n and all(0 <= a < b <= n for a, b in s)
+        assert sum(b - a for a, b in s) * 8 <= 64 * 10**6
+    assert bench.dump_slices(1 << 28) != bench.dump_slices((1 << 28) + 3)

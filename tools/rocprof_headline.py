@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Split a `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py` run into the headline's own
-dispatches: the kernel trace holds every launch of the bench (C3, C4, ring-step, other-layout, host-staged ... legs
+"""Split a `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full` run into the headline's own
+dispatches: the kernel trace holds every launch of the bench (the C3, C4, ring-step, other-layout, host-staged ... legs of --full
 use the same kernel symbol), so the headline is identified as the first warmup + steps launches, in time order,
 of `reduce_vec_kernel<float, 0, ...>` at the headline's grid (1 GiB fp32 per operand: 2^20 one-wave blocks).
 Prints one JSON object: the per-grid split of that symbol and the headline's average duration over the timed
