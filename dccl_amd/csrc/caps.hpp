@@ -117,6 +117,28 @@ constexpr WindowForm kWindowMid{1, 2, 14}, kWindowMidChain3{0, 2, 26};
 constexpr bool window_mid(bool chain, int k, size_t bytes) {
     return k >= (chain ? 3 : 4) && k <= 8 && bytes >= kWindowMidBytes && bytes < kWindowTunedBytes;
 }
+constexpr WindowForm window_mid_form(bool chain, int k) { return chain && k == 3 ? kWindowMidChain3 : kWindowMid; }
+// What launch_windows (unaligned_multi.hip) launches for k sources of `bytes` per operand, `off`: some source
+// off 16-B phase 0.  The launcher dispatches on this, tests/test_caps.py freezes it.
+enum WindowChoice : int {
+    kChoiceDefault = 0,     // per-operand tile, uncapped, tile order by the sources' phases (unaligned_order)
+    kChoiceTunedInPhase,    // window_form(kWinInPhase, k)
+    kChoiceTunedOffPhase,   // window_form(kWinOffPhase, k)
+    kChoiceMid,             // kWindowMid
+    kChoiceMidChain3,       // kWindowMidChain3
+};
+constexpr WindowChoice window_choice(bool chain, int k, size_t bytes, bool off) {
+    if (bytes >= kWindowTunedBytes) return off ? kChoiceTunedOffPhase : kChoiceTunedInPhase;
+    if (off && window_mid(chain, k, bytes)) return chain && k == 3 ? kChoiceMidChain3 : kChoiceMid;
+    return kChoiceDefault;
+}
+inline constexpr unsigned char kOrderByPhases = 255;  // kChoiceDefault's order: the launcher's unaligned_order
+constexpr WindowForm choice_form(WindowChoice c, bool chain, int k) {
+    return c == kChoiceTunedInPhase    ? window_form(kWinInPhase, k)
+           : c == kChoiceTunedOffPhase ? window_form(kWinOffPhase, k)
+           : (c == kChoiceMid || c == kChoiceMidChain3) ? window_mid_form(chain, k)
+                                       : WindowForm{0, kOrderByPhases, kUncapped};
+}
 // Element-aligned destinations with sources at other phases take reduce_windows_kernel instead of the phased
 // kernels where it led by >= 2 points: from kWindowTunedBytes at k-way k = 3..5, chain k = 4..7; mid-size with
 // the destination 16-B aligned.

@@ -8,6 +8,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #include "combine.hpp"
 #include "dccl/dccl_reduce.h"
@@ -57,6 +58,22 @@ inline bool sources_overlap_destination(const void* const* sends, int nsend, con
         if (partial_overlap(sends[k], dst, bytes)) return true;
     return own != nullptr && partial_overlap(own, dst, bytes);
 }
+
+// Test-only scale of the operand size every launcher hands to caps:: (caps.hpp): DCCL_CAPS_TEST_SHIFT = s, an
+// integer 0..12 read once per process (anything else, or unset: 0), makes an operand of `bytes` select the forms
+// of one of bytes << s, so tests/test_gpu_forms_small.py reaches the forms that start at 24, 48 and 96 MiB per
+// operand with operands of about 100 KiB.  Unset, caps_bytes is the identity.
+inline int caps_test_shift() {
+    static const int s = [] {
+        const char* e = std::getenv("DCCL_CAPS_TEST_SHIFT");
+        if (e == nullptr || *e == '\0') return 0;
+        char* end = nullptr;
+        const long x = std::strtol(e, &end, 10);
+        return (*end == '\0' && x >= 0 && x <= 12) ? int(x) : 0;
+    }();
+    return s;
+}
+inline size_t caps_bytes(size_t bytes) { return bytes << caps_test_shift(); }
 
 template <typename Fn, typename T, typename... A>
 inline int dispatch_op(int op, A&&... a) {

@@ -71,8 +71,7 @@ int reduce_typed(const void* send, void* recv, size_t count, hipStream_t stream,
     const size_t align = recv_align();
     if (ar % sizeof(T)) {  // recv's elements straddle its 16-B vectors: one 16-B access per lane at any address
         const size_t nvec = count / Pack<T>::N;
-        size_t grid = ceil_div(ceil_div(nvec, size_t(64)), size_t(8)) * 8;  // a multiple of 8 (kMaxGrid is one)
-        if (grid == 0) grid = 8;
+        size_t grid = unaligned_grid(nvec);  // a multiple of 8 (kMaxGrid is one)
         if (grid_cap && grid > grid_cap) grid = grid_cap;
         unsigned p = unsigned(as & 15);
         int order = kOrderGroup;  // one front, shared lines in one L2: +4.5 points over the XCD ranges (round 3)
@@ -121,7 +120,7 @@ int launch_multi_vec(SendList sl, unsigned char* r, Split sp, hipStream_t stream
     if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
     void* args[] = {&sl, &r, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
-                  caps::lds(caps::kMulti, K, sp.nvec * 16));
+                  caps::lds(caps::kMulti, K, caps_bytes(sp.nvec * 16)));
 }
 
 template <typename T, int OP>
@@ -147,7 +146,7 @@ int reduce_multi_typed(const void* const* sends, int nsend, void* recv, size_t c
     }
     if (!vec_ok) {  // an element-aligned recv and sources at other 16-B (or byte) phases: the phased kernel
         if constexpr (sizeof(T) > 1) {
-            if (caps::phased_via_windows(false, nsend, count * sizeof(T), (ar & 15) == 0)) {  // or the windows kernel (caps.hpp)
+            if (caps::phased_via_windows(false, nsend, caps_bytes(count * sizeof(T)), (ar & 15) == 0)) {  // or the windows kernel (caps.hpp)
                 PhaseList ph{};
                 for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
                 return multi_unaligned_typed<T, OP>(sl, ph, nsend, r, count, stream);
@@ -205,7 +204,7 @@ int launch_chain_vec(SendList sl, const unsigned char* own, unsigned char* d, Sp
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
-                  caps::lds(caps::kChain, K, sp.nvec * 16));
+                  caps::lds(caps::kChain, K, caps_bytes(sp.nvec * 16)));
 }
 
 // grid_cap: as reduce_typed's, for the zero-copy host chain combine; it applies to the in-phase launches (the host
@@ -237,7 +236,7 @@ int reduce_chain_typed(const void* const* sends, int nsend, const void* own, voi
         if constexpr (sizeof(T) > 1) {
             // or the windows kernel (caps.hpp), whose off-phase forms were measured with sources off phase (not
             // with `own` alone off phase: that launch keeps the phased kernels)
-            if (src_off && caps::phased_via_windows(true, nsend, count * sizeof(T), (ad & 15) == 0)) {
+            if (src_off && caps::phased_via_windows(true, nsend, caps_bytes(count * sizeof(T)), (ad & 15) == 0)) {
                 PhaseList ph{};
                 for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
                 ph.p[nsend] = phase_word(o, 0);
@@ -337,6 +336,10 @@ extern "C" int dccl_local_reduce_chain(const void* const* sends, int nsend, cons
                                        size_t count, int op, void* stream) {
     return local_reduce_chain_capped(sends, nsend, own, dst, dtype, count, op, static_cast<hipStream_t>(stream), 0);
 }
+
+// The active DCCL_CAPS_TEST_SHIFT (dispatch.hpp caps_test_shift; 0 unless a test set it).  For the tests only, to
+// prove their size scale is live: not part of the documented ABI, and not declared in dccl_reduce.h.
+extern "C" int dccl_caps_test_shift(void) { return caps_test_shift(); }
 
 extern "C" int dccl_copy_multi(const void* const* srcs, void* const* dsts, int npairs, size_t bytes, void* stream) {
     if (npairs < 0 || npairs > 8 || (npairs > 0 && (srcs == nullptr || dsts == nullptr))) return DCCL_INVALID_ARGUMENT;

@@ -21,7 +21,7 @@ int launch_phased(SendList sl, PhaseList ph, const unsigned char* own, unsigned 
     if constexpr (caps::phased_loads_first(true, K))
         return launch(reinterpret_cast<const void*>(
                           &reduce_chain_phased_kernel<T, OP, K, false, true, caps::tile_run(caps::kChainPhasedFirst, K)>),
-                      grid, args, stream, 64, caps::lds(caps::kChainPhasedFirst, K, sp.nvec * 16));
+                      grid, args, stream, 64, caps::lds(caps::kChainPhasedFirst, K, caps_bytes(sp.nvec * 16)));
     return launch(reinterpret_cast<const void*>(&reduce_chain_phased_kernel<T, OP, K, (K <= kPhasedXcdMaxK)>), grid, args, stream, 64);
 }
 
@@ -34,7 +34,7 @@ int launch_straddle(SendList sl, const unsigned char* own, unsigned char* d, Spl
     void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
     // the chain kernel's line-straddle caps by operand size (caps::kChainStraddle, caps.hpp)
     return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, StraddleKwayCfg>), grid, args, stream, 64,
-                  caps::lds(caps::kChainStraddle, K, sp.nvec * 16));
+                  caps::lds(caps::kChainStraddle, K, caps_bytes(sp.nvec * 16)));
 }
 
 }  // namespace

@@ -21,7 +21,7 @@ int launch_phased(SendList sl, PhaseList ph, unsigned char* r, Split sp, hipStre
     if constexpr (caps::phased_loads_first(false, K))
         return launch(reinterpret_cast<const void*>(
                           &reduce_multi_phased_kernel<T, OP, K, false, true, caps::tile_run(caps::kMultiPhasedFirst, K)>),
-                      grid, args, stream, 64, caps::lds(caps::kMultiPhasedFirst, K, sp.nvec * 16));
+                      grid, args, stream, 64, caps::lds(caps::kMultiPhasedFirst, K, caps_bytes(sp.nvec * 16)));
     return launch(reinterpret_cast<const void*>(&reduce_multi_phased_kernel<T, OP, K, (K <= kPhasedXcdMaxK)>), grid, args, stream, 64);
 }
 
@@ -35,7 +35,7 @@ int launch_straddle(SendList sl, unsigned char* r, Split sp, hipStream_t stream)
     if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
     void* args[] = {&sl, &r, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, StraddleKwayCfg<K>>), grid, args, stream, 64,
-                  caps::lds(caps::kMultiStraddle, K, sp.nvec * 16));
+                  caps::lds(caps::kMultiStraddle, K, caps_bytes(sp.nvec * 16)));
 }
 
 }  // namespace

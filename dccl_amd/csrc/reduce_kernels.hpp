@@ -13,6 +13,7 @@
 #include "caps.hpp"
 #include "combine.hpp"
 #include "dccl/dccl_reduce.h"
+#include "tile_maps.hpp"
 
 namespace dccl_amd {
 
@@ -93,39 +94,7 @@ __device__ __noinline__ void partial_tile(const u32x4* __restrict__ vs, u32x4* _
     }
 }
 
-// Bijective XCD-aware remap (cdna_hip_programming.md, "XCD swizzle must be bijective"):
-// blocks b and b+8 share an XCD, so give each group {b : b % 8 == x} one contiguous range.
-__device__ __forceinline__ size_t xcd_remap(size_t b, size_t nb) {
-    const size_t q = nb / 8, r = nb % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-// Tile-run order: in every full group of 8 RUN blocks, block 8 RUN q + r (XCD r % 8 under the round-robin
-// dispatch) takes tile 8 RUN q + RUN (r % 8) + r / 8, so each XCD walks RUN consecutive tiles of the group
-// while the groups sweep the range in order: a line two neighbouring tiles share is fetched by one L2 in
-// RUN - 1 of RUN cases.  RUN 1 is block order, RUN 8 the group-interleaved order (xcd_group_tile).  A partial
-// last group keeps the identity.  Bijective on [0, nb).
-template <int RUN>
-__device__ __forceinline__ size_t run_tile(size_t b, size_t nb) {
-    if constexpr (RUN == 1) return b;
-    constexpr size_t span = size_t(8) * RUN;
-    const size_t q = b / span, r = b % span;
-    return (q + 1) * span > nb ? b : q * span + (r % 8) * RUN + r / 8;
-}
-__device__ __forceinline__ size_t xcd_group_tile(size_t b, size_t nb) { return run_tile<8>(b, nb); }
-
-// First tile of block b of a g-block grid (g a multiple of 8) for the misaligned-destination kernels, by a
-// uniform runtime `order`: kOrderXcd gives each XCD one contiguous range (consecutive tiles on one XCD: the
-// line two tiles share meets in one L2), kOrderBlock is block order, kOrderGroup the group-interleaved order
-// above (one front for the chip, 7 of 8 tile boundaries inside one XCD).  Computed once per block.
-enum : int { kOrderXcd = 0, kOrderBlock = 1, kOrderGroup = 2, kOrderRun4 = 3, kOrderRun2 = 4 };
-__device__ __forceinline__ size_t tile_order(int order, size_t b, size_t g) {
-    return order == kOrderXcd     ? (b % 8) * (g / 8) + b / 8
-           : order == kOrderBlock ? b
-           : order == kOrderRun4  ? run_tile<4>(b, g)
-           : order == kOrderRun2  ? run_tile<2>(b, g)
-                                  : xcd_group_tile(b, g);
-}
+// The block -> tile maps (xcd_remap, run_tile<RUN>, tile_order, first_tile<ORDER>): tile_maps.hpp.
 
 template <typename T, int OP, typename C>
 __global__ __launch_bounds__(C::BLOCK) void reduce_vec_kernel(const unsigned char* __restrict__ send,
@@ -531,15 +500,6 @@ struct WindowArgs {
     size_t nvec, count;
 };
 
-template <int ORDER>
-__device__ __forceinline__ size_t first_tile(size_t b, size_t g) {
-    if constexpr (ORDER == kOrderXcd) return (b % 8) * (g / 8) + b / 8;
-    else if constexpr (ORDER == kOrderBlock) return b;
-    else if constexpr (ORDER == kOrderRun4) return run_tile<4>(b, g);
-    else if constexpr (ORDER == kOrderRun2) return run_tile<2>(b, g);
-    else return xcd_group_tile(b, g);
-}
-
 // One operand's window for vector v (the 16 bytes at byte phase p past aligned vector a[v]); all 64 lanes
 // call it (p is uniform).  FULL: v and lane 63's extra vector v + 1 lie inside the body (no bounds checks).
 template <bool FULL>
@@ -715,8 +675,6 @@ __global__ __launch_bounds__(64) void reduce_chain_unaligned_kernel(SendList sen
 // ---------------------------------------------------------------------------------
 // Host-side launch helpers
 // ---------------------------------------------------------------------------------
-constexpr size_t kMaxGrid = size_t(1) << 24;  // grid-stride beyond this (2^24 x 64 threads)
-
 inline int launch(const void* fn, size_t grid, void** args, hipStream_t stream, int block = kBlock,
                   size_t lds_bytes = 0) {
     if (grid == 0) return DCCL_SUCCESS;

@@ -11,11 +11,7 @@
 namespace dccl_amd {
 namespace {
 
-// A grid that is a multiple of 8 (the kernels' XCD / group tile maps); kMaxGrid is one.
-size_t unaligned_grid(size_t nvec) {
-    const size_t g = ceil_div(ceil_div(nvec, size_t(64)), size_t(8)) * 8;
-    return g == 0 ? 8 : g;
-}
+// Grids: unaligned_grid (tile_maps.hpp), a multiple of 8 for the kernels' XCD / group tile maps.
 
 // Tile order (1 GiB fp32 Sum, destination + 2 B, tools/ab_unaligned.py, profiles/r4_s3_ab_unaligned.json):
 // with every source at 16-B phase 0 one front for the chip wins, the group-interleaved order up to k = 2
@@ -85,12 +81,15 @@ int launch_windows(const SendList& sl, const PhaseList& ph, const unsigned char*
     A.dst = d;
     A.nvec = count / Pack<T>::N;
     A.count = count;
-    if (count * sizeof(T) >= caps::kWindowTunedBytes)
-        return off ? launch_tuned<T, OP, K, CHAIN, caps::kWinOffPhase>(A, stream)
-                   : launch_tuned<T, OP, K, CHAIN, caps::kWinInPhase>(A, stream);
-    if (off && caps::window_mid(CHAIN, K, count * sizeof(T))) {
-        constexpr caps::WindowForm f = (CHAIN && K == 3) ? caps::kWindowMidChain3 : caps::kWindowMid;
+    switch (caps::window_choice(CHAIN, K, caps_bytes(count * sizeof(T)), off)) {  // caps.hpp: the one place that chooses
+    case caps::kChoiceTunedInPhase: return launch_tuned<T, OP, K, CHAIN, caps::kWinInPhase>(A, stream);
+    case caps::kChoiceTunedOffPhase: return launch_tuned<T, OP, K, CHAIN, caps::kWinOffPhase>(A, stream);
+    case caps::kChoiceMid:
+    case caps::kChoiceMidChain3: {  // one mid-size form per (chain, K)
+        constexpr caps::WindowForm f = caps::window_mid_form(CHAIN, K);
         return launch_form<T, OP, K, CHAIN, f.first != 0, int(f.order)>(A, stream, caps::lds_for_waves(f.waves));
+    }
+    case caps::kChoiceDefault: break;
     }
     switch (unaligned_order(ph, K)) {  // smaller launches: the per-operand form, uncapped
     case kOrderXcd: return launch_form<T, OP, K, CHAIN, false, kOrderXcd>(A, stream, 0);

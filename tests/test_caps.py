@@ -49,8 +49,19 @@ int main() {
                 std::printf("%s[%d, %d, %zu, %d, %d, %d]", (ch || k > 1 || b != mids[0]) ? ", " : "", ch, k, b,
                             int(window_mid(ch, k, b)), int(phased_via_windows(ch, k, b, true)),
                             int(phased_via_windows(ch, k, b, false)));
-    std::printf("], \"mid_forms\": [%d, %d]}\n", kWindowMid.first * 1000 + kWindowMid.order * 100 + kWindowMid.waves,
+    std::printf("], \"mid_forms\": [%d, %d]", kWindowMid.first * 1000 + kWindowMid.order * 100 + kWindowMid.waves,
                 kWindowMidChain3.first * 1000 + kWindowMidChain3.order * 100 + kWindowMidChain3.waves);
+    std::printf(", \"window_choice\": [");
+    for (int ch = 0; ch < 2; ++ch)
+        for (int off = 0; off < 2; ++off)
+            for (int k = 0; k <= 8; ++k)
+                for (size_t b : mids) {
+                    const WindowChoice c = window_choice(ch, k, b, off);
+                    const WindowForm f = choice_form(c, ch, k);
+                    std::printf("%s[%d, %d, %d, %zu, %d, %d, %d, %d]", (ch || off || k || b != mids[0]) ? ", " : "", ch,
+                                off, k, b, int(c), int(f.first), int(f.order), int(f.waves));
+                }
+    std::printf("]}\n");
 }
 """
 
@@ -161,3 +172,32 @@ def test_window_mid_sizes(table):
             assert via_dst16 == want and via_not16 == want, (ch, k, b)
         else:
             assert via_dst16 == mid and via_not16 == 0, (ch, k, b)
+
+
+# window_choice (caps.hpp), frozen: what launch_windows launches.  A row is (choice, loads-first, order, waves)
+# for k = 0..8; choice 0 = default (per-operand, uncapped, order 255 = by the sources' phases), 1 = tuned in
+# phase, 2 = tuned off phase, 3 = mid, 4 = mid chain k = 3; orders 0 XCD, 1 block, 2 group, 3 runs of 4.
+_DEFAULT = [(0, 0, 255, 32)] * 9
+_TUNED_IN = [(1, 0, 1, 32)] * 3 + [(1, 0, 1, 26)] * 6
+_TUNED_OFF = [(2, 0, 0, 32)] * 3 + [(2, 0, 2, 26), (2, 1, 2, 14), (2, 1, 2, 12)] + [(2, 1, 3, 13)] * 3
+_MID_KWAY = [(0, 0, 255, 32)] * 4 + [(3, 1, 2, 14)] * 5
+_MID_CHAIN = [(0, 0, 255, 32)] * 3 + [(4, 0, 2, 26)] + [(3, 1, 2, 14)] * 5
+_MIB = 1 << 20
+WINDOW_CHOICE = {  # (chain, sources off phase) -> bytes per operand -> row
+    (0, 0): {48 * _MIB - 1: _DEFAULT, 48 * _MIB: _DEFAULT, 96 * _MIB - 1: _DEFAULT, 96 * _MIB: _TUNED_IN},
+    (0, 1): {48 * _MIB - 1: _DEFAULT, 48 * _MIB: _MID_KWAY, 96 * _MIB - 1: _MID_KWAY, 96 * _MIB: _TUNED_OFF},
+    (1, 0): {48 * _MIB - 1: _DEFAULT, 48 * _MIB: _DEFAULT, 96 * _MIB - 1: _DEFAULT, 96 * _MIB: _TUNED_IN},
+    (1, 1): {48 * _MIB - 1: _DEFAULT, 48 * _MIB: _MID_CHAIN, 96 * _MIB - 1: _MID_CHAIN, 96 * _MIB: _TUNED_OFF},
+}
+
+
+def test_window_choice(table):
+    """launch_windows dispatches on caps::window_choice: every k in 0..8, k-way and chain, sources in and off
+    phase, on both sides of 48 and 96 MiB per operand, against the frozen rows above; a capped choice is a legal
+    LDS request and the loads-first tile never runs uncapped."""
+    seen = 0
+    for ch, off, k, b, choice, first, order, waves in table["window_choice"]:
+        assert (choice, first, order, waves) == WINDOW_CHOICE[(ch, off)][b][k], (ch, off, k, b)
+        assert lds_for(waves) <= 64 << 10 and not (first and waves == 32)
+        seen += 1
+    assert seen == 2 * 2 * 9 * 4
