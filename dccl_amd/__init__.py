@@ -55,6 +55,11 @@ class ncclRedOp_t(enum.IntEnum):
     ncclAvg = 4
 
 
+class ncclScalarResidence_t(enum.IntEnum):
+    ncclScalarDevice = 0         # the scalar is device memory, read by the kernels when they run
+    ncclScalarHostImmediate = 1  # host memory, read before the call returns
+
+
 ALL_DTYPES = list(ncclDataType_t)
 ALL_OPS = [ncclRedOp_t.ncclSum, ncclRedOp_t.ncclProd, ncclRedOp_t.ncclMax, ncclRedOp_t.ncclMin]
 
@@ -93,6 +98,9 @@ def _load():
         "dccl_local_reduce_chain_host": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                  c_size_t, c_int]),
         "dccl_copy_multi": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_size_t, c_void_p]),
+        "dccl_local_scale": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
+        "dccl_local_reduce_chain_premul": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
+                                                   c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_register_host_memory": (c_int, [c_void_p, c_size_t]),
         "dccl_deregister_host_memory": (c_int, [c_void_p]),
         "dccl_size_of_type": (c_size_t, [c_int]),
@@ -113,6 +121,8 @@ def _load():
         "dccl_all_reduce": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
         "dccl_reduce_scatter": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
         "dccl_all_gather": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+        "dccl_red_op_create_premul_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
+        "dccl_red_op_destroy": (c_int, [c_int, c_void_p]),
         "dccl_rccl_available": (c_int, []),
         "dccl_bootstrap_unique_id": (c_int, [ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
         "dccl_bootstrap_done": (c_int, [ctypes.c_uint32, ctypes.c_uint32]),
@@ -143,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "dccl_comm_init_ipc", "dccl_reduce", "dccl_broadcast", "dccl_local_reduce_chain_host", "dccl_comm_init_p2p",
     "dccl_bootstrap_done", "dccl_comm_register", "dccl_comm_deregister", "dccl_ipc_stats",
     "dccl_host_reduce_gpu_min_bytes",
+    "dccl_local_scale", "dccl_local_reduce_chain_premul", "dccl_red_op_create_premul_sum", "dccl_red_op_destroy",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -191,6 +202,22 @@ def local_reduce_chain(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count:
     arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
     return int(lib.dccl_local_reduce_chain(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count), int(op),
                                            stream or None))
+
+
+def local_scale(src_ptr: int, dst_ptr: int, dtype: int, count: int, scalar_ptr: int, residence: int,
+                stream: int = 0) -> int:
+    """dst = src * scalar with Prod's element semantics (src == dst: in place).  ``scalar_ptr`` addresses one
+    element of ``dtype``: device memory read when the kernel runs (residence 0) or host memory read now (1)."""
+    return int(lib.dccl_local_scale(src_ptr, dst_ptr, int(dtype), int(count), scalar_ptr, int(residence),
+                                    stream or None))
+
+
+def local_reduce_chain_premul(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, scalar_ptr: int,
+                              residence: int, stream: int = 0) -> int:
+    """local_reduce_chain with op Sum over operands multiplied by the scalar as they are read (one pass)."""
+    arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
+    return int(lib.dccl_local_reduce_chain_premul(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
+                                                  scalar_ptr, int(residence), stream or None))
 
 
 def local_reduce_chain_host(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, op: int) -> int:
@@ -305,6 +332,17 @@ class Comm:
 
     def broadcast(self, send: int, recv: int, count: int, dtype: int, root: int, stream: int = 0) -> int:
         return int(lib.dccl_broadcast(send, recv, count, dtype, root, self.handle, stream or None))
+
+    def red_op_create_premul_sum(self, scalar_ptr: int, dtype: int, residence: int):
+        """ncclRedOpCreatePreMulSum: returns (rc, op); ``op`` is valid in all_reduce / reduce_scatter / reduce of
+        this communicator with ``dtype`` and device buffers.  Every rank must pass the same scalar value."""
+        op = ctypes.c_int(-1)
+        rc = int(lib.dccl_red_op_create_premul_sum(ctypes.byref(op), scalar_ptr, int(dtype), int(residence),
+                                                   self.handle))
+        return rc, int(op.value)
+
+    def red_op_destroy(self, op: int) -> int:
+        return int(lib.dccl_red_op_destroy(int(op), self.handle))
 
     def register(self, ptr: int, size: int) -> int:
         """dcclRegisterCacheMemory: host memory is page-locked; device memory is validated and tracked

@@ -89,6 +89,20 @@ private:
     std::atomic<uint64_t> barrier_gen_{0};  // written under bmu_, polled without it
 };
 
+// A pre-multiplied-sum op of a communicator (ncclRedOpCreatePreMulSum); handle = ncclNumOps + its slot.
+constexpr int kMaxUserOps = 16;
+struct UserOp {
+    bool live = false;
+    int dtype = 0;
+    uint64_t bits = 0;              // the scalar's bytes, read at creation (ncclScalarHostImmediate)
+    const void* dev_ptr = nullptr;  // ncclScalarDevice: read by each collective's kernels when they run
+};
+// What a collective hands down for such an op: dccl_local_scale's (scalar, residence); scalar nullptr = none.
+struct PremulArg {
+    const void* scalar = nullptr;
+    int residence = 0;
+};
+
 }  // namespace dccl_amd
 
 // The opaque communicator of include/dccl/dccl.hpp.
@@ -126,6 +140,7 @@ struct dccl::dcclComm {
     size_t dev_work_bytes = 0;
     void* host_work = nullptr;
     size_t host_work_bytes = 0;
+    dccl_amd::UserOp user_ops[dccl_amd::kMaxUserOps];  // used by the communicator's own thread only
 };
 
 namespace dccl_amd {

@@ -80,6 +80,27 @@ ncclResult_t copy_bytes(void* dst, const void* src, size_t bytes, bool device, h
     return dccl::ncclSuccess;
 }
 
+// A pre-multiplied-sum handle that is live on `c` becomes (ncclSum, its scalar); every other op value keeps
+// today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything else -> ncclInvalidArgument).
+ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, PremulArg* pm) {
+    const int slot = *op - int(dccl::ncclNumOps);
+    if (slot < 0 || slot >= kMaxUserOps || !c->user_ops[slot].live) return check_op_dtype(dtype, *op);
+    const UserOp& u = c->user_ops[slot];
+    if (u.dtype != dtype) return dccl::ncclInvalidArgument;
+    pm->scalar = u.dev_ptr != nullptr ? u.dev_ptr : static_cast<const void*>(&u.bits);
+    pm->residence = u.dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate;
+    *op = dccl::ncclSum;
+    return dccl::ncclSuccess;
+}
+
+// The collectives' first step outside the direct paths: dst = src, or dst = src * scalar for a pre-multiplied sum
+// (in place when src == dst), after which the algorithm runs with ncclSum.
+ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, const PremulArg& pm, bool device,
+                         hipStream_t st) {
+    if (pm.scalar == nullptr) return copy_bytes(dst, src, count * size_of_dtype(dtype), device, st);
+    return static_cast<ncclResult_t>(dccl_local_scale(src, dst, dtype, count, pm.scalar, pm.residence, st));
+}
+
 ncclResult_t placement(const void* send, const void* recv, bool* device) {
     const bool sd = is_device_ptr(send), rd = is_device_ptr(recv);
     if (send != nullptr && recv != nullptr && sd != rd) return dccl::ncclInvalidArgument;  // dccl.cpp:358-366
@@ -412,14 +433,17 @@ ncclResult_t dcclDeregisterCacheMemory(ncclComm_t comm, void* buffer, size_t) {
 }
 
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                           ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
+                           ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
     validate_comm(comm, __func__);
-    ncclResult_t rc = check_op_dtype(datatype, op);
+    int op = user_op;
+    PremulArg pm;
+    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
     if (rc != ncclSuccess) return rc;
     if (count == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
+    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;  // the scaling runs on the GPU only
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;  // e.g. host buffers on RCCL / IPC
     const size_t total = count * size_of_dtype(datatype);
     const uint32_t W = comm->world;
@@ -430,12 +454,13 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
         return ncclInvalidArgument;  // all_reduce_recursive_halving_and_doubling.cpp:50-54
     if (W > 1 && algo != Algorithm::kRabenseifner && (count < W || count % W)) return ncclInvalidArgument;
     if (W > 1 && dev && direct_selected(comm))
-        return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream);
+        return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, &pm);
     if (W > 1 && !dev && host_direct_selected(comm, total / W))
         return direct_all_reduce_host(comm, sendbuff, recvbuff, count, datatype, op);
-    if (W > 1 && algo != Algorithm::kRabenseifner && grouped_selected(comm, dev))
+    if (W > 1 && algo != Algorithm::kRabenseifner && pm.scalar == nullptr && grouped_selected(comm, dev))
         return all_reduce_grouped(comm, sendbuff, recvbuff, count, datatype, op, stream);
-    if ((rc = copy_bytes(recvbuff, sendbuff, total, dev, stream)) != ncclSuccess) return rc;  // dccl.cpp:393-408
+    rc = stage_input(recvbuff, sendbuff, count, datatype, pm, dev, stream);  // dccl.cpp:393-408
+    if (rc != ncclSuccess) return rc;
     if (W == 1) return ncclSuccess;
     void* scratch = nullptr;
     if (algo == Algorithm::kRabenseifner) {  // scratchpad of half the buffer (dccl.cpp:458-466)
@@ -447,26 +472,31 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
 }
 
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
-                               ncclRedOp_t op, ncclComm_t comm, hipStream_t stream) {
+                               ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
     validate_comm(comm, __func__);
-    ncclResult_t rc = check_op_dtype(datatype, op);
+    int op = user_op;
+    PremulArg pm;
+    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
     if (rc != ncclSuccess) return rc;
     if (recvcount == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
+    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
     const uint32_t W = comm->world, r = comm->rank;
     const size_t slot = recvcount * size_of_dtype(datatype), total = slot * W;
     if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream);
+        return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream, &pm);
     if (W > 1 && !dev && host_direct_selected(comm, slot))
         return direct_reduce_scatter_host(comm, sendbuff, recvbuff, recvcount, datatype, op);
-    if (W > 1 && grouped_selected(comm, dev))  // slot r, reduced straight from sendbuff: no work copy
+    // slot r, reduced straight from sendbuff: no work copy (a pre-multiplied sum scales into the work copy: the ring)
+    if (W > 1 && pm.scalar == nullptr && grouped_selected(comm, dev))
         return reduce_scatter_grouped(comm, sendbuff, recvbuff, recvcount * W, datatype, op, stream, 0);
     if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
     void* work = dev ? comm->dev_work : comm->host_work;
-    if ((rc = copy_bytes(work, sendbuff, total, dev, stream)) != ncclSuccess) return rc;  // dccl.cpp:585-609
+    rc = stage_input(work, sendbuff, recvcount * W, datatype, pm, dev, stream);  // dccl.cpp:585-609
+    if (rc != ncclSuccess) return rc;
     if (W > 1) {
         void* scratch = nullptr;
         if ((rc = ring_scratch(comm, slot, dev, &scratch)) != ncclSuccess) return rc;
@@ -479,9 +509,11 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
 }
 
 ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                        ncclRedOp_t op, int root, ncclComm_t comm, hipStream_t stream) {
+                        ncclRedOp_t user_op, int root, ncclComm_t comm, hipStream_t stream) {
     validate_comm(comm, __func__);
-    ncclResult_t rc = check_op_dtype(datatype, op);
+    int op = user_op;
+    PremulArg pm;
+    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
     if (rc != ncclSuccess) return rc;
     const uint32_t W = comm->world, r = comm->rank;
     if (root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
@@ -491,16 +523,17 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     if (sendbuff == nullptr || (iamroot && recvbuff == nullptr)) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, iamroot ? recvbuff : sendbuff, &dev)) != ncclSuccess) return rc;
+    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
     if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream);
+        return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, &pm);
     const size_t total = count * size_of_dtype(datatype), slot = total / W;
     void* rbuf = recvbuff;
     if (!iamroot) {
         if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
         rbuf = dev ? comm->dev_work : comm->host_work;
     }
-    if ((rc = copy_bytes(rbuf, sendbuff, total, dev, stream)) != ncclSuccess) return rc;
+    if ((rc = stage_input(rbuf, sendbuff, count, datatype, pm, dev, stream)) != ncclSuccess) return rc;
     if (W == 1) return ncclSuccess;
     void* scratch = nullptr;
     if ((rc = ring_scratch(comm, slot, dev, &scratch)) != ncclSuccess) return rc;
@@ -528,6 +561,34 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     }
     if ((rc = xport_send(comm, uint32_t(root), at(r), slot, dev, stream)) != ncclSuccess) return rc;
     return xport_wait_send(comm, uint32_t(root), dev, stream);
+}
+
+ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
+                                      ncclScalarResidence_t residence, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    const size_t esz = size_of_dtype(datatype);
+    if (op == nullptr || scalar == nullptr || esz == 0) return ncclInvalidArgument;
+    if (residence != ncclScalarDevice && residence != ncclScalarHostImmediate) return ncclInvalidArgument;
+    for (int slot = 0; slot < kMaxUserOps; ++slot) {
+        UserOp& u = comm->user_ops[slot];
+        if (u.live) continue;
+        u = UserOp{};
+        u.live = true;
+        u.dtype = datatype;
+        if (residence == ncclScalarDevice) u.dev_ptr = scalar;
+        else std::memcpy(&u.bits, scalar, esz);
+        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
+        return ncclSuccess;
+    }
+    return ncclInvalidUsage;  // kMaxUserOps live ops already
+}
+
+ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    const int slot = int(op) - int(ncclNumOps);
+    if (slot < 0 || slot >= kMaxUserOps || !comm->user_ops[slot].live) return ncclInvalidArgument;
+    comm->user_ops[slot] = UserOp{};
+    return ncclSuccess;
 }
 
 ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
@@ -707,6 +768,24 @@ extern "C" int dccl_broadcast(const void* send, void* recv, size_t count, int dt
     return guarded([&] {
         return dccl::ncclBroadcast(send, recv, count, static_cast<dccl::ncclDataType_t>(dtype), root,
                                    static_cast<dccl::ncclComm_t>(comm), static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm) {
+    if (residence != 0 && residence != 1) return DCCL_INVALID_ARGUMENT;  // before the cast to the two-value enum
+    return guarded([&] {
+        dccl::ncclRedOp_t h = dccl::ncclSum;
+        const ncclResult_t rc = dccl::ncclRedOpCreatePreMulSum(
+            op != nullptr ? &h : nullptr, const_cast<void*>(scalar), static_cast<dccl::ncclDataType_t>(dtype),
+            static_cast<dccl::ncclScalarResidence_t>(residence), static_cast<dccl::ncclComm_t>(comm));
+        if (rc == dccl::ncclSuccess) *op = int(h);
+        return rc;
+    });
+}
+
+extern "C" int dccl_red_op_destroy(int op, void* comm) {
+    return guarded([&] {
+        return dccl::ncclRedOpDestroy(static_cast<dccl::ncclRedOp_t>(op), static_cast<dccl::ncclComm_t>(comm));
     });
 }
 

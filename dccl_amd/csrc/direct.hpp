@@ -48,8 +48,10 @@ int ipc_stats(uint64_t* out, int n);
 // rabenseifner.
 bool direct_selected(const dccl::dcclComm* c);
 
+// `pm` (here and in direct_reduce_scatter / direct_reduce): a pre-multiplied sum (comm.hpp PremulArg; op is
+// ncclSum then): the chain launch multiplies every contribution by the scalar as it reads it.
 ncclResult_t direct_all_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
-                               hipStream_t st);
+                               hipStream_t st, const PremulArg* pm = nullptr);
 
 // Host buffers of an in-process group: the direct all_reduce with the chain combine staged through the
 // GPU (dccl_local_reduce_chain_host, staged in double-buffered pieces) and the all-gather by memcpy from
@@ -60,9 +62,9 @@ ncclResult_t direct_all_reduce_host(dccl::dcclComm* c, const void* send, void* r
 ncclResult_t direct_reduce_scatter_host(dccl::dcclComm* c, const void* send, void* recv, size_t recvcount,
                                         int dtype, int op);
 ncclResult_t direct_reduce_scatter(dccl::dcclComm* c, const void* send, void* recv, size_t recvcount, int dtype,
-                                   int op, hipStream_t st);
+                                   int op, hipStream_t st, const PremulArg* pm = nullptr);
 ncclResult_t direct_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
-                           uint32_t root, hipStream_t st);
+                           uint32_t root, hipStream_t st, const PremulArg* pm = nullptr);
 ncclResult_t direct_all_gather(dccl::dcclComm* c, const void* send, void* recv, size_t sendcount, int dtype,
                                hipStream_t st);
 ncclResult_t direct_broadcast(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype,

@@ -92,6 +92,19 @@ ncclResult_t ncclCommFinalize(ncclComm_t comm);
 ncclResult_t dcclRegisterCacheMemory(ncclComm_t comm, void* buffer, size_t size);
 ncclResult_t dcclDeregisterCacheMemory(ncclComm_t comm, void* buffer, size_t size = 0UL);
 
+/** Pre-multiplied sum (NCCL 2.11): `*op` becomes a handle (ncclNumOps + slot, up to 16 live per communicator)
+ *  that ncclAllReduce / ncclReduceScatter / ncclReduce accept on `comm` with `datatype` and device buffers:
+ *  every rank's input is multiplied by `scalar` (one element of `datatype`; with 16-bit floats the product is
+ *  rounded to 16 bits) and the products are summed, bit-identical to ncclProd against the scalar followed by the
+ *  ncclSum collective.  ncclScalarDevice: `scalar` is device memory, read by each collective's kernels when
+ *  they run; ncclScalarHostImmediate: host memory, read before this call returns.  Every rank must pass the
+ *  same value (differing scalars are undefined behaviour).  Host buffers: ncclInvalidUsage; ncclAvg stays
+ *  ncclInvalidUsage too. */
+typedef enum { ncclScalarDevice = 0, ncclScalarHostImmediate = 1 } ncclScalarResidence_t;
+ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
+                                      ncclScalarResidence_t residence, ncclComm_t comm);
+ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
+
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,

@@ -61,6 +61,21 @@
  *   dccl_all_gather       ncclAllGather       (/root/reference/include/dccl/dccl.hpp:392-393)
  *   dccl_reduce           ncclReduce          (/root/reference/include/dccl/dccl.hpp:346-347)
  *   dccl_broadcast        ncclBroadcast       (/root/reference/include/dccl/dccl.hpp:289-290)
+ *   dccl_red_op_create_premul_sum /  ncclRedOpCreatePreMulSum / ncclRedOpDestroy (NCCL 2.11): a reduction op
+ *   dccl_red_op_destroy   that multiplies every rank's input by `scalar` (one element of `dtype`) and sums
+ *                         the products, e.g. 1/W for a mean (ncclAvg itself stays ncclInvalidUsage).
+ *                         `residence` 0: the scalar lives in device memory and is read by each collective's
+ *                         kernels when they run; 1: host memory, read at creation.  The handle (5..20: up to
+ *                         16 live ops per communicator, a destroyed slot is reused) is valid in
+ *                         dccl_all_reduce / dccl_reduce_scatter / dccl_reduce on that communicator with the
+ *                         same dtype and DEVICE buffers; host buffers return ncclInvalidUsage (5) (the
+ *                         library never combines on the CPU), another dtype or a handle that is not live
+ *                         ncclInvalidArgument (4).  Every rank must pass the SAME scalar value: the direct
+ *                         collectives multiply every rank's contribution by the calling rank's scalar, so
+ *                         differing values are undefined behaviour, not an error.  Results are bit-identical
+ *                         to multiplying each input with op Prod and running the Sum collective.  Create: NULL
+ *                         op or scalar, unknown dtype or residence -> 4; a 17th live op -> 5.  Destroy: a
+ *                         built-in op (0-4) or a handle that is not live -> 4.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -89,6 +104,8 @@ int dccl_all_gather(const void* send, void* recv, size_t sendcount, int dtype, v
 int dccl_reduce(const void* send, void* recv, size_t count, int dtype, int op, int root, void* comm,
                 void* stream);
 int dccl_broadcast(const void* send, void* recv, size_t count, int dtype, int root, void* comm, void* stream);
+int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
+int dccl_red_op_destroy(int op, void* comm);
 int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);

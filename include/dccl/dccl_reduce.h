@@ -83,6 +83,29 @@ int dccl_local_reduce_chain(const void* const* sends, int nsend, const void* own
                             size_t count, int op, void* stream);
 
 /*
+ * Pre-multiplied sum (the device half of ncclRedOpCreatePreMulSum, include/dccl/dccl.hpp): every contribution
+ * is multiplied by one scalar s of the operands' dtype, then summed.
+ *   dccl_local_scale                 dst[i] = Prod(src[i], s); src == dst scales in place
+ *   dccl_local_reduce_chain_premul   dccl_local_reduce_chain with op Sum over Prod(sends[j][i], s) and
+ *                                    Prod(own[i], s), in the same order and roles, in one pass
+ * Prod and Sum are the element semantics above, each rounded on its own: integers wrap, fp32 / fp64 take one
+ * IEEE multiply and then one IEEE add (never a fused multiply-add), fp16 / bf16 products are rounded to
+ * 16 bits before they enter the sum.  The results are therefore bit-identical to dccl_local_reduce with
+ * op Prod against a buffer filled with s, followed by the Sum combine (NaN payloads unpinned, as everywhere).
+ * `scalar` points to one element of `dtype`; `residence` 0: device memory, read by the kernel when it runs
+ * (stream-ordered: a captured graph replays with the value the memory holds then); 1: host memory, read
+ * before the call returns.  Validation, in this order: unknown dtype 4; nsend outside 1..8 or NULL sends 4;
+ * residence not 0 / 1 or NULL scalar 4; count == 0 succeeds; NULL operand 4; an operand partially
+ * overlapping dst 4 (src == dst, own == dst and a source == dst are allowed); launch failure 1.
+ * Operands that are element-aligned and share dst's 16-byte phase take 16-byte vector kernels; any other
+ * placement (operands off element alignment included) takes an element-wise kernel kept for correctness.
+ */
+int dccl_local_scale(const void* src, void* dst, int dtype, size_t count, const void* scalar, int residence,
+                     void* stream);
+int dccl_local_reduce_chain_premul(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
+                                   size_t count, const void* scalar, int residence, void* stream);
+
+/*
  * Multi-source device copy: dsts[y][0..bytes) = srcs[y][0..bytes) for y < npairs (<= 8), in one
  * launch, so the reads of several peers' chunks use several xGMI links at once (the all-gather
  * half of the direct collectives; replaces W-1 ring all-gather steps,

@@ -53,6 +53,24 @@ static void cpu_checks(void) {
     CHECK(dccl_local_reduce_multi(ov, 1, c, 7, 4, 0, NULL) == DCCL_INVALID_ARGUMENT);
     CHECK(dccl_local_reduce_chain(sends, 1, c + 3, c, 7, 4, 0, NULL) == DCCL_INVALID_ARGUMENT);
     CHECK(dccl_local_reduce_chain_host(ov, 1, a, c, 7, 4, 0) == DCCL_INVALID_ARGUMENT);
+    /* pre-multiplied sum: dtype, nsend, scalar / residence, count 0, NULL operands, overlap, in that order */
+    const float half = 0.5f;
+    CHECK(dccl_local_scale(a, b, 11, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_scale(a, b, 7, 4, &half, 2, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_scale(a, b, 7, 4, NULL, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_scale(NULL, NULL, 7, 0, &half, 1, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_scale(NULL, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_scale(c + 1, c, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(sends, 1, a, b, 11, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(sends, 9, a, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(sends, 1, a, b, 7, 4, &half, -1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(sends, 1, a, b, 7, 0, &half, 0, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_reduce_chain_premul(sends, 1, NULL, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(ov, 1, a, c, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_premul(sends, 1, c + 3, c, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    int premul_op = 0;
+    CHECK(dccl_red_op_create_premul_sum(&premul_op, &half, 7, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null comm */
+    CHECK(dccl_red_op_destroy(5, NULL) == DCCL_INVALID_ARGUMENT);
     /* routing hint: the reference has no host loop for bf16 / fp16 */
     CHECK(dccl_host_reduce_gpu_min_bytes(9) == 0 && dccl_host_reduce_gpu_min_bytes(6) == 0);
 }
