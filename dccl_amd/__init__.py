@@ -10,6 +10,7 @@ Enum values are those of the reference's public header
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import enum
 import os
@@ -81,6 +82,12 @@ P2P_EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_
                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p)
 
 
+class dccl_copy_rows_t(ctypes.Structure):
+    """One segment of dccl_copy_rows_multi (include/dccl/dccl_reduce.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_size_t),
+                ("src_stride", ctypes.c_size_t), ("dst_stride", ctypes.c_size_t)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -98,6 +105,8 @@ def _load():
         "dccl_local_reduce_chain_host": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                  c_size_t, c_int]),
         "dccl_copy_multi": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_size_t, c_void_p]),
+        "dccl_copy_rows_multi": (c_int, [ctypes.POINTER(dccl_copy_rows_t), c_int, ctypes.c_uint32, c_void_p]),
+        "dccl_copy_rows_check": (c_int, [ctypes.POINTER(dccl_copy_rows_t), c_int, ctypes.c_uint32]),
         "dccl_local_scale": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_local_reduce_chain_premul": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                    c_size_t, c_void_p, c_int, c_void_p]),
@@ -129,6 +138,9 @@ def _load():
         "dccl_comm_register": (c_int, [c_void_p, c_void_p, c_size_t]),
         "dccl_comm_deregister": (c_int, [c_void_p, c_void_p]),
         "dccl_ipc_stats": (c_int, [ctypes.POINTER(ctypes.c_uint64), c_int]),
+        "dccl_group_start": (c_int, []),
+        "dccl_group_end": (c_int, []),
+        "dccl_group_stats": (c_int, [ctypes.POINTER(ctypes.c_uint64), c_int]),
         "dccl_synth_fill": (c_int, [c_void_p, c_int, c_size_t, c_int, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
         "dccl_synth_fill_range": (c_int, [c_void_p, c_int, c_size_t, c_int, ctypes.c_uint64, ctypes.c_uint64,
                                           c_size_t, c_void_p]),
@@ -154,6 +166,7 @@ EXPORTED_SYMBOLS = [
     "dccl_bootstrap_done", "dccl_comm_register", "dccl_comm_deregister", "dccl_ipc_stats",
     "dccl_host_reduce_gpu_min_bytes",
     "dccl_local_scale", "dccl_local_reduce_chain_premul", "dccl_red_op_create_premul_sum", "dccl_red_op_destroy",
+    "dccl_copy_rows_multi", "dccl_copy_rows_check", "dccl_group_start", "dccl_group_end", "dccl_group_stats",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -172,6 +185,40 @@ def ipc_stats() -> dict:
     n = int(lib.dccl_ipc_stats(buf, len(IPC_STAT_NAMES)))
     assert n == len(IPC_STAT_NAMES), (n, len(IPC_STAT_NAMES))
     return dict(zip(IPC_STAT_NAMES, (int(v) for v in buf)))
+
+
+#: names of the dccl_group_stats counters, in order (include/dccl/dccl_comm.h)
+GROUP_STAT_NAMES = ["groups", "calls_queued", "collectives_issued", "coalesced_runs", "tensors_coalesced",
+                    "bytes_packed"]
+
+
+def group_stats() -> dict:
+    """This process's group counters (dccl_group_stats) by name."""
+    buf = (ctypes.c_uint64 * len(GROUP_STAT_NAMES))()
+    n = int(lib.dccl_group_stats(buf, len(GROUP_STAT_NAMES)))
+    assert n == len(GROUP_STAT_NAMES), (n, len(GROUP_STAT_NAMES))
+    return dict(zip(GROUP_STAT_NAMES, (int(v) for v in buf)))
+
+
+def group_start() -> int:
+    """ncclGroupStart: collectives of this thread are queued until the matching outermost group_end()."""
+    return int(lib.dccl_group_start())
+
+
+def group_end() -> int:
+    """ncclGroupEnd: the outermost one executes the queue and returns its first error (5 without a start)."""
+    return int(lib.dccl_group_end())
+
+
+@contextlib.contextmanager
+def group():
+    """``with dccl_amd.group(): ...`` = group_start() ... group_end(); a failing group_end raises DcclError."""
+    check(group_start(), "dccl_group_start")
+    try:
+        yield
+    finally:
+        rc = group_end()
+    check(rc, "dccl_group_end")
 
 
 def result_string(code: int) -> str:
@@ -232,6 +279,24 @@ def copy_multi(src_ptrs, dst_ptrs, nbytes: int, stream: int = 0) -> int:
     s = (ctypes.c_void_p * max(1, n))(*src_ptrs)
     d = (ctypes.c_void_p * max(1, n))(*dst_ptrs)
     return int(lib.dccl_copy_multi(s, d, n, int(nbytes), stream or None))
+
+
+def _rows_array(segs):
+    arr = (dccl_copy_rows_t * max(1, len(segs)))()
+    for i, (src, dst, row_bytes, src_stride, dst_stride) in enumerate(segs):
+        arr[i] = dccl_copy_rows_t(src or None, dst or None, row_bytes, src_stride, dst_stride)
+    return arr
+
+
+def copy_rows_multi(segs, rows: int, stream: int = 0) -> int:
+    """Batched strided row copy, one launch: ``segs`` is a list of (src, dst, row_bytes, src_stride, dst_stride);
+    row r < rows of every segment goes from src + r * src_stride to dst + r * dst_stride."""
+    return int(lib.dccl_copy_rows_multi(_rows_array(segs), len(segs), int(rows), stream or None))
+
+
+def copy_rows_check(segs, rows: int) -> int:
+    """The validation of copy_rows_multi alone (0 or 4); launches nothing."""
+    return int(lib.dccl_copy_rows_check(_rows_array(segs), len(segs), int(rows)))
 
 
 def host_reduce_gpu_min_bytes(dtype: int) -> int:

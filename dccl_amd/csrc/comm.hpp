@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "dccl/dccl.hpp"
+#include "dccl/dccl_reduce.h"
 
 namespace dccl_amd {
 
@@ -140,6 +141,13 @@ struct dccl::dcclComm {
     size_t dev_work_bytes = 0;
     void* host_work = nullptr;
     size_t host_work_bytes = 0;
+    // Pack buffer of the coalesced groups (dccl_api.cpp): the packed tensors of one run, and a
+    // reduce-scatter's packed result behind them.  Its own allocation: the ring reduce-scatter and the non-root
+    // reduce that run ON it already use dev_work.
+    void* dev_pack = nullptr;
+    size_t dev_pack_bytes = 0;
+    hipEvent_t dev_pack_done = nullptr;  // recorded behind each run's unpack: the next run's pack waits for it
+    hipEvent_t dev_pack_join = nullptr;  // joins the other streams of a run to the run's stream, and back
     dccl_amd::UserOp user_ops[dccl_amd::kMaxUserOps];  // used by the communicator's own thread only
 };
 
@@ -170,6 +178,10 @@ inline ncclResult_t p2p_exchange(dccl::dcclComm* c, const void* sendbuf, size_t 
 // Scratch management (grown on demand, page/line rounded; never shrinks until finalize).
 ncclResult_t ensure_scratch(dccl::dcclComm* c, size_t bytes, bool device);
 ncclResult_t ensure_work(dccl::dcclComm* c, size_t bytes, bool device);
+ncclResult_t ensure_pack(dccl::dcclComm* c, size_t bytes);  // device memory; dev_pack_bytes changes when it grew
+
+// dccl_copy_rows_multi's launch without its validation (copy_rows.hip), for plans disjoint by construction.
+int copy_rows_launch(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, hipStream_t stream);
 
 // Test-only fault injection: DCCL_FAULT_INJECT=<site>:<rank> makes `site` fail on that rank, so the
 // tests can check that one rank's failure reaches every member of the group (as an error) instead of

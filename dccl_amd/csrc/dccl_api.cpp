@@ -9,6 +9,8 @@
 //   ncclAllGather      :849-862  copy into own slot, ring AG
 //   ncclSend/Recv      :865-911  one transfer, waited
 //   ncclBroadcast/Bcast:701-743  root -> every rank
+// ncclGroupStart / ncclGroupEnd (the reference has neither) queue these calls per thread and run them at the
+// outermost end; consecutive small reductions are packed and run as one collective (group_plan.hpp).
 // Deliberate differences: op/dtype are validated before any buffer is touched
 // (ncclAvg -> ncclInvalidUsage even at W = 1; unknown dtype -> ncclInvalidArgument), a null comm
 // throws std::runtime_error for every call (the reference's VALIDATE_COMM, dccl.cpp:32-36),
@@ -16,6 +18,8 @@
 // buffers.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -30,6 +34,7 @@
 #include "bootstrap.hpp"
 #include "comm.hpp"
 #include "direct.hpp"
+#include "group_plan.hpp"
 #include "rccl_transport.hpp"
 #include "dccl/dccl.hpp"
 #include "dccl/dccl_comm.h"
@@ -377,6 +382,8 @@ ncclResult_t dcclCommInitRank(ncclComm_t* comm, uint32_t world_size, uint32_t ra
 ncclResult_t ncclCommFinalize(ncclComm_t comm) {
     validate_comm(comm, __func__);
     ncclResult_t rc = ncclSuccess;
+    // A C caller without the HIP headers has no other way to wait for the device: tools/c_abi_check.c relies on
+    // this synchronisation before it reads what dccl_copy_rows_multi wrote.
     if (comm->device >= 0 && hipDeviceSynchronize() != hipSuccess) rc = ncclUnhandledCudaError;
     if (comm->rccl != nullptr) {
         const int r = rccl_comm_destroy(comm->rccl);
@@ -393,6 +400,9 @@ ncclResult_t ncclCommFinalize(ncclComm_t comm) {
         if (e) (void)hipEventDestroy(e);
     if (comm->dev_scratch) (void)hipFree(comm->dev_scratch);
     if (comm->dev_work) (void)hipFree(comm->dev_work);
+    if (comm->dev_pack) (void)hipFree(comm->dev_pack);
+    if (comm->dev_pack_done) (void)hipEventDestroy(comm->dev_pack_done);
+    if (comm->dev_pack_join) (void)hipEventDestroy(comm->dev_pack_join);
     for (void* h : {comm->host_scratch, comm->host_work}) {
         if (h) {
             (void)hipHostUnregister(h);
@@ -432,9 +442,39 @@ ncclResult_t dcclDeregisterCacheMemory(ncclComm_t comm, void* buffer, size_t) {
     return ncclSuccess;
 }
 
-ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                           ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
-    validate_comm(comm, __func__);
+}  // namespace dccl
+
+namespace {
+using namespace dccl;
+
+// One validated collective call: what "validate" leaves for "run", and what a group queues.
+struct Call {
+    int api = 0;               // group::Api
+    dcclComm* comm = nullptr;
+    const void* send = nullptr;
+    void* recv = nullptr;
+    size_t count = 0;          // as the call counts: recvcount for a reduce-scatter, sendcount for an all-gather
+    int dtype = 0;
+    int user_op = 0;           // the op value as passed (a pre-multiplied-sum handle included): the run key
+    int op = 0;                // resolved: a built-in op
+    PremulArg pm;              // resolved: the pre-multiplied sum's scalar, or none
+    uint64_t bits = 0;         // a queued host-immediate scalar's own copy
+    int root = 0;
+    bool dev = false;
+    Algorithm algo = Algorithm::kRing;  // ncclAllReduce: DCCL_ALLREDUCE_ALGORITHM when the call was validated
+    hipStream_t stream = nullptr;
+    bool bits_live = false;
+};
+
+// ------------------------------------------------------------------------------------------
+// Every collective is "validate" (its checks, in their order, with their return values, unchanged; it leaves a
+// Call) and "run" (the collective's body on a Call).  Outside a group a call is validate + run; inside one it is
+// validate + queue, and the outermost ncclGroupEnd runs the queue (below).
+// ------------------------------------------------------------------------------------------
+ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                         ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
+    validate_comm(comm, "ncclAllReduce");
+    *todo = false;
     int op = user_op;
     PremulArg pm;
     ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
@@ -445,7 +485,6 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
     if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;  // the scaling runs on the GPU only
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;  // e.g. host buffers on RCCL / IPC
-    const size_t total = count * size_of_dtype(datatype);
     const uint32_t W = comm->world;
     const Algorithm algo = allreduce_algorithm();  // dccl.cpp:412-413,454
     if (algo == Algorithm::kUnknown) return ncclInvalidUsage;
@@ -453,6 +492,33 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     if (W > 1 && algo == Algorithm::kRabenseifner && count % (1u << floor_log2_u32(W)))
         return ncclInvalidArgument;  // all_reduce_recursive_halving_and_doubling.cpp:50-54
     if (W > 1 && algo != Algorithm::kRabenseifner && (count < W || count % W)) return ncclInvalidArgument;
+    *c = Call{group::kAllReduce, comm, sendbuff, recvbuff, count, datatype, user_op, op, pm, 0, 0, dev, algo, nullptr};
+    *todo = true;
+    return ncclSuccess;
+}
+
+// True when ar_run's dispatch below ends in all_reduce_rabenseifner for this call: the name alone does not decide,
+// the direct forms come first.  run_packed cuts its buffer into the slots of the algorithm that RUNS.
+bool runs_rabenseifner(const Call& c) {
+    const ncclComm_t comm = c.comm;
+    if (c.api != group::kAllReduce || c.algo != Algorithm::kRabenseifner || comm->world <= 1) return false;
+    if (c.dev && direct_selected(comm)) return false;
+    if (!c.dev && host_direct_selected(comm, c.count * size_of_dtype(c.dtype) / comm->world)) return false;
+    return true;
+}
+
+ncclResult_t ar_run(const Call& c, hipStream_t stream) {
+    const ncclComm_t comm = c.comm;
+    const void* sendbuff = c.send;
+    void* recvbuff = c.recv;
+    const size_t count = c.count;
+    const int datatype = c.dtype, op = c.op;
+    const PremulArg& pm = c.pm;
+    const bool dev = c.dev;
+    const Algorithm algo = c.algo;
+    const size_t total = count * size_of_dtype(datatype);
+    const uint32_t W = comm->world;
+    ncclResult_t rc;
     if (W > 1 && dev && direct_selected(comm))
         return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, &pm);
     if (W > 1 && !dev && host_direct_selected(comm, total / W))
@@ -463,7 +529,7 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     if (rc != ncclSuccess) return rc;
     if (W == 1) return ncclSuccess;
     void* scratch = nullptr;
-    if (algo == Algorithm::kRabenseifner) {  // scratchpad of half the buffer (dccl.cpp:458-466)
+    if (runs_rabenseifner(c)) {  // scratchpad of half the buffer (dccl.cpp:458-466)
         if ((rc = ring_scratch(comm, total / 2, dev, &scratch)) != ncclSuccess) return rc;
         return all_reduce_rabenseifner(comm, recvbuff, scratch, count, datatype, op, dev, stream);
     }
@@ -471,9 +537,10 @@ ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, n
     return all_reduce_ring(comm, recvbuff, scratch, count, datatype, op, dev, stream);
 }
 
-ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
-                               ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
-    validate_comm(comm, __func__);
+ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
+                         ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
+    validate_comm(comm, "ncclReduceScatter");
+    *todo = false;
     int op = user_op;
     PremulArg pm;
     ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
@@ -484,6 +551,21 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
     if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
+    *c = Call{group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype, user_op, op, pm, 0, 0, dev,
+              Algorithm::kRing, nullptr};
+    *todo = true;
+    return ncclSuccess;
+}
+
+ncclResult_t rs_run(const Call& c, hipStream_t stream) {
+    const ncclComm_t comm = c.comm;
+    const void* sendbuff = c.send;
+    void* recvbuff = c.recv;
+    const size_t recvcount = c.count;
+    const int datatype = c.dtype, op = c.op;
+    const PremulArg& pm = c.pm;
+    const bool dev = c.dev;
+    ncclResult_t rc;
     const uint32_t W = comm->world, r = comm->rank;
     const size_t slot = recvcount * size_of_dtype(datatype), total = slot * W;
     if (W > 1 && dev && direct_selected(comm))
@@ -508,9 +590,10 @@ ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recv
     return copy_bytes(recvbuff, static_cast<unsigned char*>(work) + size_t(r) * slot, slot, dev, stream);
 }
 
-ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                        ncclRedOp_t user_op, int root, ncclComm_t comm, hipStream_t stream) {
-    validate_comm(comm, __func__);
+ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                             ncclRedOp_t user_op, int root, ncclComm_t comm, Call* c, bool* todo) {
+    validate_comm(comm, "ncclReduce");
+    *todo = false;
     int op = user_op;
     PremulArg pm;
     ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
@@ -525,6 +608,23 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     if ((rc = placement(sendbuff, iamroot ? recvbuff : sendbuff, &dev)) != ncclSuccess) return rc;
     if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
+    *c = Call{group::kReduce, comm, sendbuff, recvbuff, count, datatype, user_op, op, pm, 0, root, dev,
+              Algorithm::kRing, nullptr};
+    *todo = true;
+    return ncclSuccess;
+}
+
+ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
+    const ncclComm_t comm = c.comm;
+    const void* sendbuff = c.send;
+    void* recvbuff = c.recv;
+    const size_t count = c.count;
+    const int datatype = c.dtype, op = c.op, root = c.root;
+    const PremulArg& pm = c.pm;
+    const bool dev = c.dev;
+    ncclResult_t rc;
+    const uint32_t W = comm->world, r = comm->rank;
+    const bool iamroot = r == uint32_t(root);
     if (W > 1 && dev && direct_selected(comm))
         return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, &pm);
     const size_t total = count * size_of_dtype(datatype), slot = total / W;
@@ -563,6 +663,294 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
     return xport_wait_send(comm, uint32_t(root), dev, stream);
 }
 
+ncclResult_t ag_validate(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
+                         ncclComm_t comm, Call* c, bool* todo) {
+    validate_comm(comm, "ncclAllGather");
+    *todo = false;
+    const size_t esz = size_of_dtype(datatype);
+    if (esz == 0) return ncclInvalidArgument;
+    if (sendcount == 0) return ncclSuccess;
+    if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
+    bool dev = false;
+    ncclResult_t rc = placement(sendbuff, recvbuff, &dev);
+    if (rc != ncclSuccess) return rc;
+    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
+    *c = Call{group::kAllGather, comm, sendbuff, recvbuff, sendcount, datatype, 0, 0, PremulArg{}, 0, 0, dev,
+              Algorithm::kRing, nullptr};
+    *todo = true;
+    return ncclSuccess;
+}
+
+ncclResult_t ag_run(const Call& c, hipStream_t stream) {
+    const ncclComm_t comm = c.comm;
+    const size_t esz = size_of_dtype(c.dtype);
+    if (comm->world > 1 && c.dev && direct_selected(comm))
+        return direct_all_gather(comm, c.send, c.recv, c.count, c.dtype, stream);
+    void* slot = static_cast<unsigned char*>(c.recv) + c.count * comm->rank * esz;
+    ncclResult_t rc;
+    if ((rc = copy_bytes(slot, c.send, c.count * esz, c.dev, stream)) != ncclSuccess) return rc;
+    const RankMap id = [](uint32_t x) { return x; };
+    return all_gather_ring(comm, c.recv, c.count, c.dtype, c.dev, stream, id, id);
+}
+
+ncclResult_t bcast_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                            ncclComm_t comm, Call* c, bool* todo) {
+    validate_comm(comm, "ncclBroadcast");
+    *todo = false;
+    const size_t esz = size_of_dtype(datatype);
+    const uint32_t W = comm->world, r = comm->rank;
+    if (esz == 0 || root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
+    if (count == 0) return ncclSuccess;
+    bool dev = false;
+    ncclResult_t rc = placement(r == uint32_t(root) ? sendbuff : recvbuff, recvbuff, &dev);
+    if (rc != ncclSuccess) return rc;
+    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
+    *c = Call{group::kBroadcast, comm, sendbuff, recvbuff, count, datatype, 0, 0, PremulArg{}, 0, root, dev,
+              Algorithm::kRing, nullptr};
+    *todo = true;
+    return ncclSuccess;
+}
+
+ncclResult_t bcast_run(const Call& c, hipStream_t stream) {
+    const ncclComm_t comm = c.comm;
+    const void* sendbuff = c.send;
+    void* recvbuff = c.recv;
+    const size_t count = c.count;
+    const int datatype = c.dtype, root = c.root;
+    const bool dev = c.dev;
+    const uint32_t W = comm->world, r = comm->rank;
+    const size_t bytes = count * size_of_dtype(datatype);
+    ncclResult_t rc = ncclSuccess;
+    if (W > 1 && dev && direct_selected(comm))
+        return direct_broadcast(comm, sendbuff, recvbuff, count, datatype, uint32_t(root), stream);
+    if (comm->p2p != nullptr) {  // root -> every rank, one exchange per peer (RCCL: one group)
+        if (r != uint32_t(root)) return p2p_exchange(comm, nullptr, 0, 0, recvbuff, bytes, uint32_t(root), stream);
+        if (comm->rccl != nullptr) {
+            std::vector<void*> bufs(W, const_cast<void*>(sendbuff));
+            rc = static_cast<ncclResult_t>(rccl_fan(comm->rccl, true, bufs.data(), bytes, W, r, stream));
+            return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
+        }
+        for (uint32_t p = 0; p < W && rc == ncclSuccess; ++p)
+            if (p != r) rc = p2p_exchange(comm, sendbuff, bytes, p, nullptr, 0, 0, stream);
+        return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
+    }
+    if (r == uint32_t(root)) {
+        for (uint32_t p = 0; p < W; ++p)
+            if (p != r && (rc = xport_send(comm, p, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
+        if ((rc = copy_bytes(recvbuff, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
+        for (uint32_t p = 0; p < W; ++p)
+            if (p != r && (rc = xport_wait_send(comm, p, dev, stream)) != ncclSuccess) return rc;
+        return ncclSuccess;
+    }
+    return xport_recv(comm, uint32_t(root), recvbuff, bytes, dev, stream);
+}
+
+ncclResult_t run_plain(const Call& c) {
+    switch (c.api) {
+    case group::kAllReduce: return ar_run(c, c.stream);
+    case group::kReduceScatter: return rs_run(c, c.stream);
+    case group::kReduce: return reduce_run(c, c.stream);
+    case group::kAllGather: return ag_run(c, c.stream);
+    default: return bcast_run(c, c.stream);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Group state (per thread) and execution.
+// ------------------------------------------------------------------------------------------
+thread_local int tl_depth = 0;
+thread_local std::vector<Call> tl_queue;
+
+// groups ended, calls queued, collectives issued, coalesced runs, tensors coalesced, bytes packed
+std::atomic<uint64_t> g_group_stats[6];
+
+// DCCL_GROUP_COALESCE=0: no packing; DCCL_GROUP_COALESCE_MAX_BYTES: tensors of that many bytes or more are never
+// packed.  Read at every ncclGroupEnd; the same on every rank (the plan depends on them).
+size_t coalesce_max_bytes() {
+    const char* off = std::getenv("DCCL_GROUP_COALESCE");
+    if (off != nullptr && off[0] == '0' && off[1] == '\0') return 0;
+    const char* e = std::getenv("DCCL_GROUP_COALESCE_MAX_BYTES");
+    if (e != nullptr && *e != '\0') {
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(e, &end, 10);
+        if (*end == '\0') return static_cast<size_t>(v);
+    }
+    return group::kDefaultMaxBytes;
+}
+
+// Inside a group: a validated call joins the queue.  The scalar of a host-immediate pre-multiplied sum is kept in
+// the entry itself (run_queue points the entry's PremulArg at it), so nothing refers to the op's slot later.
+ncclResult_t enqueue(Call c, hipStream_t stream) {
+    c.stream = stream;
+    if (c.pm.scalar != nullptr && c.pm.residence == ncclScalarHostImmediate) {
+        std::memcpy(&c.bits, c.pm.scalar, sizeof c.bits);
+        c.pm.scalar = nullptr;  // set again when the entry has its final address
+        c.bits_live = true;
+    }
+    tl_queue.push_back(c);
+    g_group_stats[1].fetch_add(1, std::memory_order_relaxed);
+    return ncclSuccess;
+}
+
+ncclResult_t hip_rc(hipError_t e) {
+    if (e == hipSuccess) return ncclSuccess;
+    (void)hipGetLastError();
+    return ncclUnhandledCudaError;
+}
+
+// `to` waits for everything enqueued on `from` so far.  One event of the communicator serves every join: a wait
+// refers to the record that precedes it, and the communicator's thread issues them one after the other.
+ncclResult_t stream_join(dcclComm* comm, hipStream_t from, hipStream_t to) {
+    if (comm->dev_pack_join == nullptr) {
+        const ncclResult_t rc = hip_rc(hipEventCreateWithFlags(&comm->dev_pack_join, hipEventDisableTiming));
+        if (rc != ncclSuccess) return rc;
+    }
+    const ncclResult_t rc = hip_rc(hipEventRecord(comm->dev_pack_join, from));
+    return rc == ncclSuccess ? hip_rc(hipStreamWaitEvent(to, comm->dev_pack_join, 0)) : rc;
+}
+
+inline void keep_first(ncclResult_t* first, ncclResult_t rc) {
+    if (*first == ncclSuccess) *first = rc;
+}
+
+// One coalesced run (group_plan.hpp): pack -> the ordinary collective on the packed buffer -> unpack, on the
+// stream of the run's first call.  The collective always runs, whatever failed before it on this rank: the
+// peers are in it.
+ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
+    const Call& c0 = calls[0];
+    dcclComm* comm = c0.comm;
+    const uint32_t W = comm->world;
+    const size_t esz = size_of_dtype(c0.dtype);
+    const size_t P = group::slots_of(W, runs_rabenseifner(c0));
+    const group::Layout L = group::pack_layout(plan, n, P);
+    const bool rs = c0.api == group::kReduceScatter;
+    const size_t bytes = P * L.S + (rs ? L.S : 0);
+    hipStream_t st = c0.stream;
+    const size_t had = comm->dev_pack_bytes;
+    ncclResult_t rc = ensure_pack(comm, bytes);
+    // Known limit: without the buffer there is nothing to run the collective on, so a rank whose allocation fails
+    // returns here while its peers enter the collective and wait for it, exactly as a plain ncclReduceScatter or
+    // non-root ncclReduce whose ensure_work fails does today ("Known limit").
+    if (rc != ncclSuccess) return rc;
+    ncclResult_t first = ncclSuccess;
+    if (comm->dev_pack_bytes != had)  // new or grown (hipFree drained the device): no pad byte is read uninitialised
+        keep_first(&first, hip_rc(hipMemsetAsync(comm->dev_pack, 0, comm->dev_pack_bytes, st)));
+    else if (comm->dev_pack_done != nullptr)  // the last run's unpack, maybe on another stream, still reads the buffer
+        keep_first(&first, hip_rc(hipStreamWaitEvent(st, comm->dev_pack_done, 0)));
+    unsigned char* pack = static_cast<unsigned char*>(comm->dev_pack);
+    std::vector<hipStream_t> others;
+    for (size_t i = 1; i < n; ++i)
+        if (calls[i].stream != st && std::find(others.begin(), others.end(), calls[i].stream) == others.end())
+            others.push_back(calls[i].stream);
+    for (hipStream_t o : others) keep_first(&first, stream_join(comm, o, st));
+    dccl_copy_rows_t segs[group::kMaxRun];
+    for (size_t i = 0; i < n; ++i) segs[i] = {calls[i].send, pack + L.off[i], L.slot[i], L.slot[i], L.S};
+    keep_first(&first, static_cast<ncclResult_t>(copy_rows_launch(segs, int(n), uint32_t(P), st)));
+    Call pc = c0;
+    pc.send = pack;
+    pc.recv = rs ? pack + P * L.S : pack;
+    pc.count = rs ? L.S / esz : L.count;
+    pc.stream = st;
+    const ncclResult_t crc = run_plain(pc);
+    keep_first(&first, crc);
+    g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
+    g_group_stats[3].fetch_add(1, std::memory_order_relaxed);
+    g_group_stats[4].fetch_add(n, std::memory_order_relaxed);
+    size_t packed = 0;
+    for (size_t i = 0; i < n; ++i) packed += P * L.slot[i];
+    g_group_stats[5].fetch_add(packed, std::memory_order_relaxed);
+    if (crc == ncclSuccess && (c0.api != group::kReduce || comm->rank == uint32_t(c0.root))) {
+        for (size_t i = 0; i < n; ++i) {
+            if (rs) segs[i] = {pack + P * L.S + L.off[i], calls[i].recv, L.slot[i], 0, 0};
+            else segs[i] = {pack + L.off[i], calls[i].recv, L.slot[i], L.S, L.slot[i]};
+        }
+        keep_first(&first, static_cast<ncclResult_t>(copy_rows_launch(segs, int(n), rs ? 1u : uint32_t(P), st)));
+    }
+    for (hipStream_t o : others) keep_first(&first, stream_join(comm, st, o));
+    if (comm->dev_pack_done == nullptr)
+        keep_first(&first, hip_rc(hipEventCreateWithFlags(&comm->dev_pack_done, hipEventDisableTiming)));
+    if (comm->dev_pack_done != nullptr) keep_first(&first, hip_rc(hipEventRecord(comm->dev_pack_done, st)));
+    return first;
+}
+
+// The outermost ncclGroupEnd: every queued item executes, in issue order, even after an error (a collective
+// never leaves a peer waiting); the first error is returned.
+ncclResult_t run_queue(std::vector<Call>& q) {
+    for (Call& c : q)
+        if (c.bits_live) c.pm.scalar = &c.bits;
+    std::vector<group::Call> plan(q.size());
+    for (size_t i = 0; i < q.size(); ++i) {
+        const Call& c = q[i];
+        const uint32_t W = c.comm->world;
+        plan[i].api = c.api;
+        plan[i].comm = c.comm;
+        plan[i].esz = size_of_dtype(c.dtype);
+        plan[i].count = c.api == group::kReduceScatter ? c.count * W : c.count;
+        plan[i].dtype = c.dtype;
+        plan[i].op = c.user_op;
+        plan[i].root = c.root;
+        plan[i].device = c.dev;
+        plan[i].world = W;
+    }
+    ncclResult_t first = ncclSuccess;
+    for (const group::Run& r : group::plan_runs(plan.data(), plan.size(), coalesce_max_bytes())) {
+        if (r.packed) {
+            keep_first(&first, run_packed(&q[r.first], &plan[r.first], r.n));
+            continue;
+        }
+        for (size_t i = r.first; i < r.first + r.n; ++i) {
+            keep_first(&first, run_plain(q[i]));
+            g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
+        }
+    }
+    return first;
+}
+
+}  // namespace
+
+namespace dccl {
+
+ncclResult_t ncclGroupStart() {
+    ++tl_depth;
+    return ncclSuccess;
+}
+
+ncclResult_t ncclGroupEnd() {
+    if (tl_depth == 0) return ncclInvalidUsage;
+    if (--tl_depth > 0) return ncclSuccess;
+    std::vector<Call> q;
+    q.swap(tl_queue);  // the queue and the depth are clear whatever happens below
+    g_group_stats[0].fetch_add(1, std::memory_order_relaxed);
+    return run_queue(q);
+}
+
+ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                           ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
+    Call c;
+    bool todo = false;
+    const ncclResult_t rc = ar_validate(sendbuff, recvbuff, count, datatype, user_op, comm, &c, &todo);
+    if (rc != ncclSuccess || !todo) return rc;
+    return tl_depth > 0 ? enqueue(c, stream) : ar_run(c, stream);
+}
+
+ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
+                               ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
+    Call c;
+    bool todo = false;
+    const ncclResult_t rc = rs_validate(sendbuff, recvbuff, recvcount, datatype, user_op, comm, &c, &todo);
+    if (rc != ncclSuccess || !todo) return rc;
+    return tl_depth > 0 ? enqueue(c, stream) : rs_run(c, stream);
+}
+
+ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                        ncclRedOp_t user_op, int root, ncclComm_t comm, hipStream_t stream) {
+    Call c;
+    bool todo = false;
+    const ncclResult_t rc = reduce_validate(sendbuff, recvbuff, count, datatype, user_op, root, comm, &c, &todo);
+    if (rc != ncclSuccess || !todo) return rc;
+    return tl_depth > 0 ? enqueue(c, stream) : reduce_run(c, stream);
+}
+
 ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
                                       ncclScalarResidence_t residence, ncclComm_t comm) {
     validate_comm(comm, __func__);
@@ -593,57 +981,20 @@ ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
 
 ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
                            ncclComm_t comm, hipStream_t stream) {
-    validate_comm(comm, __func__);
-    const size_t esz = size_of_dtype(datatype);
-    if (esz == 0) return ncclInvalidArgument;
-    if (sendcount == 0) return ncclSuccess;
-    if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
-    bool dev = false;
-    ncclResult_t rc = placement(sendbuff, recvbuff, &dev);
-    if (rc != ncclSuccess) return rc;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    if (comm->world > 1 && dev && direct_selected(comm))
-        return direct_all_gather(comm, sendbuff, recvbuff, sendcount, datatype, stream);
-    void* slot = static_cast<unsigned char*>(recvbuff) + sendcount * comm->rank * esz;
-    if ((rc = copy_bytes(slot, sendbuff, sendcount * esz, dev, stream)) != ncclSuccess) return rc;
-    const RankMap id = [](uint32_t x) { return x; };
-    return all_gather_ring(comm, recvbuff, sendcount, datatype, dev, stream, id, id);
+    Call c;
+    bool todo = false;
+    const ncclResult_t rc = ag_validate(sendbuff, recvbuff, sendcount, datatype, comm, &c, &todo);
+    if (rc != ncclSuccess || !todo) return rc;
+    return tl_depth > 0 ? enqueue(c, stream) : ag_run(c, stream);
 }
 
 ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
                            ncclComm_t comm, hipStream_t stream) {
-    validate_comm(comm, __func__);
-    const size_t esz = size_of_dtype(datatype);
-    const uint32_t W = comm->world, r = comm->rank;
-    if (esz == 0 || root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
-    if (count == 0) return ncclSuccess;
-    const size_t bytes = count * esz;
-    bool dev = false;
-    ncclResult_t rc = placement(r == uint32_t(root) ? sendbuff : recvbuff, recvbuff, &dev);
-    if (rc != ncclSuccess) return rc;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    if (W > 1 && dev && direct_selected(comm))
-        return direct_broadcast(comm, sendbuff, recvbuff, count, datatype, uint32_t(root), stream);
-    if (comm->p2p != nullptr) {  // root -> every rank, one exchange per peer (RCCL: one group)
-        if (r != uint32_t(root)) return p2p_exchange(comm, nullptr, 0, 0, recvbuff, bytes, uint32_t(root), stream);
-        if (comm->rccl != nullptr) {
-            std::vector<void*> bufs(W, const_cast<void*>(sendbuff));
-            rc = static_cast<ncclResult_t>(rccl_fan(comm->rccl, true, bufs.data(), bytes, W, r, stream));
-            return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
-        }
-        for (uint32_t p = 0; p < W && rc == ncclSuccess; ++p)
-            if (p != r) rc = p2p_exchange(comm, sendbuff, bytes, p, nullptr, 0, 0, stream);
-        return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
-    }
-    if (r == uint32_t(root)) {
-        for (uint32_t p = 0; p < W; ++p)
-            if (p != r && (rc = xport_send(comm, p, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
-        if ((rc = copy_bytes(recvbuff, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
-        for (uint32_t p = 0; p < W; ++p)
-            if (p != r && (rc = xport_wait_send(comm, p, dev, stream)) != ncclSuccess) return rc;
-        return ncclSuccess;
-    }
-    return xport_recv(comm, uint32_t(root), recvbuff, bytes, dev, stream);
+    Call c;
+    bool todo = false;
+    const ncclResult_t rc = bcast_validate(sendbuff, recvbuff, count, datatype, root, comm, &c, &todo);
+    if (rc != ncclSuccess || !todo) return rc;
+    return tl_depth > 0 ? enqueue(c, stream) : bcast_run(c, stream);
 }
 
 ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,
@@ -654,6 +1005,7 @@ ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int ro
 ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                       hipStream_t stream) {
     validate_comm(comm, __func__);
+    if (tl_depth > 0) return ncclInvalidUsage;  // no grouped point-to-point (include/dccl/dccl.hpp)
     const size_t esz = size_of_dtype(datatype);
     if (esz == 0 || peer < 0 || uint32_t(peer) >= comm->world || uint32_t(peer) == comm->rank)
         return ncclInvalidArgument;  // dccl.cpp:869-872
@@ -669,6 +1021,7 @@ ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatyp
 ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                       hipStream_t stream) {
     validate_comm(comm, __func__);
+    if (tl_depth > 0) return ncclInvalidUsage;  // no grouped point-to-point (include/dccl/dccl.hpp)
     const size_t esz = size_of_dtype(datatype);
     if (esz == 0 || peer < 0 || uint32_t(peer) >= comm->world || uint32_t(peer) == comm->rank)
         return ncclInvalidArgument;  // dccl.cpp:893-896
@@ -802,6 +1155,21 @@ extern "C" int dccl_comm_deregister(void* comm, void* buffer) {
 extern "C" int dccl_ipc_stats(uint64_t* out, int n) {
     if (out == nullptr && n > 0) return -1;
     return ipc_stats(out, n);
+}
+
+extern "C" int dccl_group_start(void) {
+    return guarded([&] { return dccl::ncclGroupStart(); });
+}
+
+extern "C" int dccl_group_end(void) {
+    return guarded([&] { return dccl::ncclGroupEnd(); });
+}
+
+extern "C" int dccl_group_stats(uint64_t* out, int n) {
+    if (out == nullptr && n > 0) return -1;
+    const int count = int(sizeof(g_group_stats) / sizeof(g_group_stats[0]));
+    for (int i = 0; i < n && i < count; ++i) out[i] = g_group_stats[i].load(std::memory_order_relaxed);
+    return count;
 }
 
 extern "C" int dccl_bootstrap_unique_id(uint32_t rank, uint32_t world, void* id128) {

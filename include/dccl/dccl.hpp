@@ -122,6 +122,23 @@ ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatyp
 ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                       hipStream_t stream);
 
+/** Group calls (NCCL's): between ncclGroupStart and the matching outermost ncclGroupEnd, ncclAllReduce,
+ *  ncclReduceScatter, ncclReduce, ncclAllGather, ncclBroadcast and ncclBcast on the calling thread are validated
+ *  as always (an invalid call returns its error at once and is not queued), queued, and return ncclSuccess; the
+ *  outermost ncclGroupEnd executes the queue in issue order, every item even after an error, and returns the
+ *  first error.  Nesting is counted per thread; ncclGroupEnd without a start is ncclInvalidUsage.  Buffers must
+ *  stay valid until the outermost ncclGroupEnd returns, and a pre-multiplied-sum op must not be destroyed before it
+ *  (its host scalar was read when it was created; the handle is resolved when the call is queued).
+ *  Coalescing: consecutive reductions of device buffers with the same api, communicator, datatype, op (and root)
+ *  whose payloads are each below DCCL_GROUP_COALESCE_MAX_BYTES are packed, at most 32 at a time, into one
+ *  library-owned buffer and run as ONE collective on the stream of the first call (streams of later calls are
+ *  joined by events); results are the separate calls' bits.  DCCL_GROUP_COALESCE=0 turns packing
+ *  off.  Both variables must have the same value on every rank: the plan must be the same everywhere.
+ *  ncclSend / ncclRecv inside a group return ncclInvalidUsage: the in-process transport keeps one outstanding
+ *  device message per peer at W <= 2, so a deadlock-free grouped point-to-point needs transport work. */
+ncclResult_t ncclGroupStart();
+ncclResult_t ncclGroupEnd();
+
 uint32_t dcclGetWorldSize(ncclComm_t comm);
 uint32_t dcclGetMyRank(ncclComm_t comm);
 

@@ -76,6 +76,21 @@
  *                         to multiplying each input with op Prod and running the Sum collective.  Create: NULL
  *                         op or scalar, unknown dtype or residence -> 4; a 17th live op -> 5.  Destroy: a
  *                         built-in op (0-4) or a handle that is not live -> 4.
+ *   dccl_group_start /    ncclGroupStart / ncclGroupEnd (include/dccl/dccl.hpp): between them, on the calling thread,
+ *   dccl_group_end        dccl_all_reduce / dccl_reduce_scatter / dccl_reduce / dccl_all_gather / dccl_broadcast are
+ *                         validated as always (an invalid call returns its usual code at once and is not queued),
+ *                         then queued, and return 0; the outermost dccl_group_end executes the queue in issue order
+ *                         and returns the first error after executing everything.  dccl_group_end without a start
+ *                         -> 5.  Buffers stay valid until the outermost end returns.  Consecutive reductions of
+ *                         device buffers with the same communicator, dtype, op (and root) and fewer than
+ *                         DCCL_GROUP_COALESCE_MAX_BYTES bytes each are packed and run as ONE collective, at most 32
+ *                         tensors at a time, with the bits of the separate calls;
+ *                         DCCL_GROUP_COALESCE=0 turns the packing off.  Both variables must be the same on every
+ *                         rank.  Point-to-point calls inside a group return 5: a deadlock-free grouped send/recv
+ *                         needs more than the one outstanding device message per peer the in-process transport has.
+ *   dccl_group_stats      process-wide counters, in this order: outermost groups ended, calls queued, collectives
+ *                         actually issued by group ends, coalesced runs, tensors coalesced, bytes packed.  Fills
+ *                         min(n, count) values; returns count.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -110,6 +125,9 @@ int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);
 int dccl_ipc_stats(uint64_t* out, int n);
+int dccl_group_start(void);
+int dccl_group_end(void);
+int dccl_group_stats(uint64_t* out, int n);
 #ifdef __cplusplus
 }
 #endif

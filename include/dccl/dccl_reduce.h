@@ -114,6 +114,33 @@ int dccl_local_reduce_chain_premul(const void* const* sends, int nsend, const vo
 int dccl_copy_multi(const void* const* srcs, void* const* dsts, int npairs, size_t bytes, void* stream);
 
 /*
+ * Batched strided row copy, one launch: for every segment i < nsegs (<= 32), every row r < rows and every byte
+ * b < row_bytes,  dst[r * dst_stride + b] = src[r * src_stride + b].  It is the pack and unpack of a coalesced
+ * group (ncclGroupStart / ncclGroupEnd): packing tensor i of a group into slot-major order is
+ * {send_i, pack + off_i, slot_i, slot_i, S} with rows = the slot count, unpacking is the mirror image.  Any byte
+ * alignment of either side; every destination row is written in aligned 16-byte vectors with bytewise head and
+ * tail.  Validation, in this order and before any HIP call: nsegs outside 0..32, NULL segs with nsegs > 0 or
+ * rows == 0 -> 4; nsegs == 0 succeeds; a NULL src or dst of a segment with row_bytes > 0 -> 4; a stride below
+ * row_bytes with rows > 1 -> 4; a destination byte that is also a source byte (its own segment's included) or
+ * another destination's byte -> 4 (an exact test: destinations that interleave without sharing a byte, as a
+ * pack's do, are accepted); launch failure 1.  The overlap test is closed-form for one-row sets and for equal
+ * strides (every pack and unpack); segments of different strides whose bounding boxes meet are swept row by row
+ * over the side with fewer rows inside the other's box, which costs host time in proportion to that count.
+ * dccl_copy_rows_check answers the validation alone (0 or 4) and launches nothing.  It is not one of NCCL's or
+ * the reference's entry points: it exists so that a caller, and this project's tests, can tell "accepted" from
+ * "rejected" on addresses that must not be dereferenced, which dccl_copy_rows_multi cannot show without launching.
+ */
+typedef struct {
+    const void* src;
+    void* dst;
+    size_t row_bytes;
+    size_t src_stride;
+    size_t dst_stride;
+} dccl_copy_rows_t;
+int dccl_copy_rows_multi(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, void* stream);
+int dccl_copy_rows_check(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows);
+
+/*
  * Host combine, synchronous: `send` and `recv` are host pointers (the RDMA
  * receive buffers of the reference's host path).  Replaces the reference's CPU
  * boundary do_host_reduce<DT>

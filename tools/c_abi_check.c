@@ -71,6 +71,36 @@ static void cpu_checks(void) {
     int premul_op = 0;
     CHECK(dccl_red_op_create_premul_sum(&premul_op, &half, 7, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null comm */
     CHECK(dccl_red_op_destroy(5, NULL) == DCCL_INVALID_ARGUMENT);
+    /* batched row copy: every validation case answers before any device work (never-dereferenced addresses) */
+    {
+        char* const base = (char*)(uintptr_t)0x100000000000ull;
+        dccl_copy_rows_t seg[2] = {{base, base + 4096, 100, 100, 256}, {base + 1024, base + 4096 + 100, 28, 28, 256}};
+        CHECK(dccl_copy_rows_multi(seg, -1, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_copy_rows_multi(seg, 33, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_copy_rows_multi(NULL, 1, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_copy_rows_multi(seg, 2, 0, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_copy_rows_multi(NULL, 0, 4, NULL) == DCCL_SUCCESS);
+        CHECK(dccl_copy_rows_check(seg, 2, 4) == DCCL_SUCCESS); /* a pack: the destinations interleave */
+        seg[1].dst = base + 4096 + 99;                          /* one shared byte */
+        CHECK(dccl_copy_rows_multi(seg, 2, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        seg[1].dst = base + 4096 + 100;
+        seg[1].dst_stride = 27; /* a stride below row_bytes */
+        CHECK(dccl_copy_rows_multi(seg, 2, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_copy_rows_check(seg, 2, 1) == DCCL_SUCCESS); /* one row: strides are not looked at */
+        seg[0].src = NULL;
+        CHECK(dccl_copy_rows_multi(seg, 2, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    }
+    /* group calls: depth per thread, an invalid call inside a group answers at once */
+    {
+        uint64_t st0[6] = {0}, st1[6] = {0};
+        CHECK(dccl_group_stats(st0, 6) == 6);
+        CHECK(dccl_group_end() == DCCL_INVALID_USAGE);
+        CHECK(dccl_group_start() == DCCL_SUCCESS && dccl_group_start() == DCCL_SUCCESS);
+        CHECK(dccl_all_reduce(a, b, 4, 7, 0, NULL, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_group_end() == DCCL_SUCCESS && dccl_group_end() == DCCL_SUCCESS);
+        CHECK(dccl_group_end() == DCCL_INVALID_USAGE);
+        CHECK(dccl_group_stats(st1, 6) == 6 && st1[0] == st0[0] + 1 && st1[1] == st0[1]);
+    }
     /* routing hint: the reference has no host loop for bf16 / fp16 */
     CHECK(dccl_host_reduce_gpu_min_bytes(9) == 0 && dccl_host_reduce_gpu_min_bytes(6) == 0);
 }
@@ -100,6 +130,32 @@ static void gpu_checks(void) {
     CHECK(dccl_local_reduce_host(si, ri, 0, N, 1) == DCCL_SUCCESS);
     CHECK(memcmp(ri, wanti, N) == 0);
     free(s), free(r), free(want), free(si), free(ri), free(wanti);
+    /* one small batched row copy on page-locked host memory (the kernel reads and writes it in place); finalizing a
+     * communicator waits for the device */
+    enum { ROWS = 3, PAGE = 4096 };
+    unsigned char* m = aligned_alloc(PAGE, 2 * PAGE);
+    void* comm = NULL;
+    if (!m) {
+        failures++;
+        return;
+    }
+    for (int i = 0; i < 2 * PAGE; ++i) m[i] = (unsigned char)(i < PAGE ? i * 31 + 7 : 0xee);
+    CHECK(dccl_register_host_memory(m, 2 * PAGE) == DCCL_SUCCESS);
+    CHECK(dccl_comm_init_rank(&comm, 1, 0) == DCCL_SUCCESS);
+    const dccl_copy_rows_t seg[2] = {{m + 3, m + PAGE + 5, 37, 37, 128}, {m + 200, m + PAGE + 5 + 37, 17, 17, 128}};
+    CHECK(dccl_copy_rows_multi(seg, 2, ROWS, NULL) == DCCL_SUCCESS);
+    /* the only device synchronisation a C caller has: ncclCommFinalize waits for the device (dccl_api.cpp says so
+     * at that call); without it the comparison below would race the kernel */
+    CHECK(dccl_comm_finalize(comm) == DCCL_SUCCESS);
+    for (int i = 0; i < PAGE; ++i) {
+        unsigned char want_b = 0xee;
+        const int row = (i - 5) / 128, b = (i - 5) % 128;
+        if (i >= 5 && row < ROWS && b < 37) want_b = m[3 + row * 37 + b];
+        else if (i >= 5 && row < ROWS && b < 37 + 17) want_b = m[200 + row * 17 + (b - 37)];
+        CHECK(m[PAGE + i] == want_b);
+    }
+    CHECK(dccl_deregister_host_memory(m) == DCCL_SUCCESS);
+    free(m);
 }
 
 int main(int argc, char** argv) {

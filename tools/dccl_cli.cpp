@@ -14,6 +14,10 @@
 // parse_reduce_operation drops `== 0` after the first strcmp, cli.cpp:167-182, so `prod`
 // becomes Max and `max`/`min`/`avg` become Prod: documented deviation).
 //
+// -G <n>: every repetition issues n buffers of -c elements (buffer j memset(rank + j)) inside one
+// ncclGroupStart / ncclGroupEnd; the row then also reports the mean latency per group ("us_per_group") and the
+// hash runs over all n outputs.  DCCL_GROUP_COALESCE=0 gives the same group without packing.
+//
 // Output: one JSON line per rank: first element's bits, whether the buffer is uniform, an
 // FNV-1a hash of the whole buffer and the mean latency per call.
 #include <hip/hip_runtime.h>
@@ -41,6 +45,7 @@ struct Opts {
     bool multi_gpu = false;
     long warmup = 0, repeat = 1000, count = 1024;
     int world = 1;
+    int group = 0;         // -G: buffers per group (0: no group calls)
     bool process = false;  // -p: this process is one rank (ncclCommInit)
     int rank = 0;          // -p: from the environment
     ncclDataType_t dtype = ncclUint32;
@@ -84,21 +89,29 @@ void run_rank(const Opts& o, int rank, Result* out) {
     }
     ncclComm_t comm = nullptr;
     if ((out->rc = o.process ? ncclCommInit(&comm) : dcclCommInitRank(&comm, o.world, rank)) != ncclSuccess) return;
-    void *send = nullptr, *recv = nullptr;
+    const int nbuf = o.group > 0 ? o.group : 1;
+    std::vector<void*> sends(nbuf, nullptr), recvs(nbuf, nullptr);
     hipStream_t stream = nullptr;
-    if (o.gpu < 0) {
-        if (posix_memalign(&send, 64, nbytes + 64) || posix_memalign(&recv, 64, nbytes + 64)) { out->rc = 2; return; }
-        std::memset(send, rank, nbytes);
-        std::memset(recv, rank + 128, nbytes);
-        (void)dcclRegisterCacheMemory(comm, send, (nbytes + 63) / 64 * 64);
-    } else {
-        if (hipMalloc(&send, nbytes + 128) != hipSuccess || hipMalloc(&recv, nbytes + 128) != hipSuccess ||
-            hipStreamCreate(&stream) != hipSuccess || hipMemset(send, rank, nbytes) != hipSuccess ||
-            hipMemset(recv, rank, nbytes) != hipSuccess) { out->rc = 1; return; }
+    if (o.gpu >= 0 && hipStreamCreate(&stream) != hipSuccess) { out->rc = 1; return; }
+    for (int j = 0; j < nbuf; ++j) {
+        void *&send = sends[j], *&recv = recvs[j];
+        if (o.gpu < 0) {
+            if (posix_memalign(&send, 64, nbytes + 64) || posix_memalign(&recv, 64, nbytes + 64)) { out->rc = 2; return; }
+            std::memset(send, rank + j, nbytes);
+            std::memset(recv, rank + j + 128, nbytes);
+            (void)dcclRegisterCacheMemory(comm, send, (nbytes + 63) / 64 * 64);
+        } else {
+            if (hipMalloc(&send, nbytes + 128) != hipSuccess || hipMalloc(&recv, nbytes + 128) != hipSuccess ||
+                hipMemset(send, rank + j, nbytes) != hipSuccess || hipMemset(recv, rank + j, nbytes) != hipSuccess) {
+                out->rc = 1;
+                return;
+            }
+        }
     }
-    auto* sb = static_cast<unsigned char*>(send);
     const size_t slot_off = size_t(rank) * nbytes / o.world;
-    auto once = [&]() -> ncclResult_t {
+    auto one = [&](int j) -> ncclResult_t {
+        void *send = sends[j], *recv = recvs[j];
+        auto* sb = static_cast<unsigned char*>(send);
         if (o.api == "all_reduce") return ncclAllReduce(send, send, o.count, o.dtype, o.op, comm, stream);
         if (o.api == "reduce_scatter")
             return ncclReduceScatter(send, sb + slot_off, o.count / o.world, o.dtype, o.op, comm, stream);
@@ -109,6 +122,16 @@ void run_rank(const Opts& o, int rank, Result* out) {
         if (o.api == "recv") return rank < 2 ? ncclRecv(send, o.count, o.dtype, 1 - rank, comm, stream) : ncclSuccess;
         return ncclInvalidArgument;
     };
+    auto once = [&]() -> ncclResult_t {
+        if (o.group <= 0) return one(0);
+        ncclResult_t rc = ncclGroupStart();
+        for (int j = 0; j < nbuf; ++j) {
+            const ncclResult_t r1 = one(j);
+            if (rc == ncclSuccess) rc = r1;
+        }
+        const ncclResult_t r2 = ncclGroupEnd();  // always: the depth must return to 0
+        return rc == ncclSuccess ? r2 : rc;
+    };
     for (long i = 0; i < o.warmup && out->rc == 0; ++i) out->rc = once();
     if (stream) (void)hipStreamSynchronize(stream);
     const auto t0 = std::chrono::steady_clock::now();
@@ -116,19 +139,23 @@ void run_rank(const Opts& o, int rank, Result* out) {
     if (stream) (void)hipStreamSynchronize(stream);
     const auto t1 = std::chrono::steady_clock::now();
     out->us_per_call = o.repeat ? std::chrono::duration<double, std::micro>(t1 - t0).count() / o.repeat : 0;
-    out->bytes.resize(nbytes);
-    const void* result = (o.api == "broadcast") ? recv : send;
-    if (o.gpu < 0) std::memcpy(out->bytes.data(), result, nbytes);
-    else if (hipMemcpy(out->bytes.data(), result, nbytes, hipMemcpyDeviceToHost) != hipSuccess) out->rc = 1;
-    if (o.gpu < 0) {
-        (void)dcclDeregisterCacheMemory(comm, send);
-        std::free(send);
-        std::free(recv);
-    } else {
-        (void)hipFree(send);
-        (void)hipFree(recv);
-        (void)hipStreamDestroy(stream);
+    out->bytes.resize(nbytes * nbuf);
+    for (int j = 0; j < nbuf; ++j) {
+        void *send = sends[j], *recv = recvs[j];
+        const void* result = (o.api == "broadcast") ? recv : send;
+        unsigned char* to = out->bytes.data() + size_t(j) * nbytes;
+        if (o.gpu < 0) std::memcpy(to, result, nbytes);
+        else if (hipMemcpy(to, result, nbytes, hipMemcpyDeviceToHost) != hipSuccess) out->rc = 1;
+        if (o.gpu < 0) {
+            (void)dcclDeregisterCacheMemory(comm, send);
+            std::free(send);
+            std::free(recv);
+        } else {
+            (void)hipFree(send);
+            (void)hipFree(recv);
+        }
     }
+    if (stream) (void)hipStreamDestroy(stream);
     const ncclResult_t frc = ncclCommFinalize(comm);
     if (out->rc == 0) out->rc = frc;
 }
@@ -142,10 +169,10 @@ int main(int argc, char** argv) {
                                  {"type", required_argument, 0, 't'},   {"op", required_argument, 0, 'o'},
                                  {"count", required_argument, 0, 'c'},  {"world", required_argument, 0, 'n'},
                                  {"multi-gpu", no_argument, 0, 'm'},    {"help", no_argument, 0, 'h'},
-                                 {"process", no_argument, 0, 'p'},
+                                 {"process", no_argument, 0, 'p'},    {"group", required_argument, 0, 'G'},
                                  {0, 0, 0, 0}};
     int c;
-    while ((c = getopt_long(argc, argv, "a:g:w:r:t:o:c:n:mph", lo, nullptr)) != -1) {
+    while ((c = getopt_long(argc, argv, "a:g:w:r:t:o:c:n:G:mph", lo, nullptr)) != -1) {
         switch (c) {
         case 'a': o.api = optarg; break;
         case 'g': o.gpu = std::atoi(optarg); break;
@@ -153,13 +180,14 @@ int main(int argc, char** argv) {
         case 'r': o.repeat = std::atol(optarg); break;
         case 'c': o.count = std::atol(optarg); break;
         case 'n': o.world = std::atoi(optarg); break;
+        case 'G': o.group = std::atoi(optarg); break;
         case 'm': o.multi_gpu = true; break;
         case 'p': o.process = true; break;
         case 't': if (!parse_dtype(optarg, &o.dtype)) { std::fprintf(stderr, "unknown type %s\n", optarg); return 1; } break;
         case 'o': if (!parse_op(optarg, &o.op)) { std::fprintf(stderr, "unknown op %s\n", optarg); return 1; } break;
         default:
             std::printf("usage: %s -a {all_reduce,reduce_scatter,all_gather,reduce,broadcast,send,recv} "
-                        "[-t type] [-o op] [-c count] [-w warmup] [-r repeat] [-g gpu|-1] [-n world] [-m] [-p]\n", argv[0]);
+                        "[-t type] [-o op] [-c count] [-w warmup] [-r repeat] [-g gpu|-1] [-n world] [-G buffers per group] [-m] [-p]\n", argv[0]);
             return c == 'h' ? 0 : 1;
         }
     }
@@ -176,7 +204,10 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    if (o.api.empty() || o.world < 1 || o.count < 0) { std::fprintf(stderr, "missing/invalid -a/-n/-c\n"); return 1; }
+    if (o.api.empty() || o.world < 1 || o.count < 0 || o.group < 0) {
+        std::fprintf(stderr, "missing/invalid -a/-n/-c/-G\n");
+        return 1;
+    }
     const int first_rank = o.process ? o.rank : 0, ranks = o.process ? 1 : o.world;
     std::vector<Result> res(ranks);
     std::vector<std::thread> th;
@@ -194,10 +225,13 @@ int main(int argc, char** argv) {
             for (size_t i = esz; i < x.bytes.size() && uniform; i += esz)
                 uniform = std::memcmp(x.bytes.data(), x.bytes.data() + i, esz) == 0;
         }
-        std::printf("{\"rank\": %d, \"rc\": %d, \"first\": \"0x%0*llx\", \"uniform\": %s, \"fnv1a\": \"0x%016llx\", "
-                    "\"us_per_call\": %.3f}\n",
+        std::printf("{\"rank\": %d, \"rc\": %d, \"first\": \"0x%0*llx\", \"uniform\": %s, \"fnv1a\": \"0x%016llx\", ",
                     r, x.rc, int(esz * 2), static_cast<unsigned long long>(first), uniform ? "true" : "false",
-                    static_cast<unsigned long long>(fnv1a(x.bytes.data(), x.bytes.size())), x.us_per_call);
+                    static_cast<unsigned long long>(fnv1a(x.bytes.data(), x.bytes.size())));
+        if (o.group > 0)  // a repetition is one group of o.group calls
+            std::printf("\"group\": %d, \"us_per_group\": %.3f, \"us_per_call\": %.3f}\n", o.group, x.us_per_call,
+                        x.us_per_call / o.group);
+        else std::printf("\"us_per_call\": %.3f}\n", x.us_per_call);
         if (x.rc) rc = 2;
     }
     return rc;

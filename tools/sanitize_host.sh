@@ -18,7 +18,7 @@ for f in comm algorithms grouped bootstrap dccl_api direct host_staged rccl_tran
 done
 # the kernel translation units are reused from the normal build (their host side is launchers only)
 lr=("$root/build/obj/local_reduce.hip.o" "$root/build/obj/phased_multi.hip.o" "$root/build/obj/phased_chain.hip.o"
-    "$root/build/obj/unaligned_multi.hip.o" "$root/build/obj/premul.hip.o")
+    "$root/build/obj/unaligned_multi.hip.o" "$root/build/obj/premul.hip.o" "$root/build/obj/copy_rows.hip.o")
 for o in "${lr[@]}"; do [[ -f "$o" ]] || python "$root/dccl_amd/build.py" > /dev/null; done
 "$HIPCC" "${flags[@]}" -c "$root/tools/dccl_cli.cpp" -o "$out/cli.o"
 "$HIPCC" --offload-arch=gfx950 -Xarch_host "-fsanitize=$kind" "$out/cli.o" "${objs[@]}" "${lr[@]}" -o "$out/dccl_cli" -pthread -ldl
@@ -30,4 +30,7 @@ run -a all_gather -t float64 -c 3003 -n 3 -r 5 -g -1
 run -a broadcast -t int8 -c 65536 -n 8 -r 10 -g -1
 run -a all_reduce -t float32 -c 1024 -n 1 -r 5 -g -1
 run -a all_gather -t uint64 -c 8 -n 2 -r 50 -g -1
+# group calls: the per-thread queue and its execution at the outermost ncclGroupEnd
+run -a all_gather -t uint32 -c 3003 -n 3 -r 10 -g -1 -G 5
+run -a broadcast -t int8 -c 4096 -n 4 -r 10 -g -1 -G 3
 echo "sanitize_host($kind): clean"
