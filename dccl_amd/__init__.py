@@ -116,6 +116,9 @@ def _load():
         "dccl_host_reduce_gpu_min_bytes": (c_size_t, [c_int]),
         "dccl_result_string": (ctypes.c_char_p, [c_int]),
         "dccl_version": (c_int, []),
+        # test-only reports of DCCL_CAPS_TEST_SHIFT and DCCL_MAX_GRID_TEST (0: inactive); not in the documented ABI
+        "dccl_caps_test_shift": (c_int, []),
+        "dccl_max_grid_test": (c_int, []),
     }
     sig.update({
         "dccl_comm_init_rank": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_uint32, ctypes.c_uint32]),

@@ -68,7 +68,8 @@ __attribute__((visibility("hidden"))) int copy_rows_launch(const dccl_copy_rows_
     }
     size_t grid = rows_prefix(rl.row_bytes, nsegs, rows, rl.pre);
     if (grid == 0) return DCCL_SUCCESS;  // nothing but empty rows
-    if (grid > (size_t(1) << 20)) grid = size_t(1) << 20;  // copy_multi_kernel's cap; the blocks stride
+    const size_t cap = max_grid() < (size_t(1) << 20) ? max_grid() : size_t(1) << 20;
+    if (grid > cap) grid = cap;  // copy_multi_kernel's cap; the blocks stride
     void* args[] = {&rl, &nsegs};
     return hipLaunchKernel(reinterpret_cast<const void*>(&copy_rows_kernel), dim3(unsigned(grid)), dim3(64), args, 0,
                            stream) == hipSuccess

@@ -63,6 +63,9 @@ inline bool sources_overlap_destination(const void* const* sends, int nsend, con
 // integer 0..12 read once per process (anything else, or unset: 0), makes an operand of `bytes` select the forms
 // of one of bytes << s, so tests/test_gpu_forms_small.py reaches the forms that start at 24, 48 and 96 MiB per
 // operand with operands of about 100 KiB.  Unset, caps_bytes is the identity.
+// Its companion is DCCL_MAX_GRID_TEST (tile_maps.hpp max_grid): a multiple of 8 from 8 to kMaxGrid, read once per
+// process, clamps the grid of every combine and copy launch, so tests/test_gpu_grid_stride_small.py runs the
+// grid-stride passes that otherwise start at 16 GiB per operand.  dccl_max_grid_test() reports it (0: no clamp).
 inline int caps_test_shift() {
     static const int s = [] {
         const char* e = std::getenv("DCCL_CAPS_TEST_SHIFT");

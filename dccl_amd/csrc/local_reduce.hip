@@ -340,6 +340,9 @@ extern "C" int dccl_local_reduce_chain(const void* const* sends, int nsend, cons
 // The active DCCL_CAPS_TEST_SHIFT (dispatch.hpp caps_test_shift; 0 unless a test set it).  For the tests only, to
 // prove their size scale is live: not part of the documented ABI, and not declared in dccl_reduce.h.
 extern "C" int dccl_caps_test_shift(void) { return caps_test_shift(); }
+// The active DCCL_MAX_GRID_TEST (tile_maps.hpp max_grid): 0 when no test clamp is active, else the clamp.  For the
+// tests only, like dccl_caps_test_shift.
+extern "C" int dccl_max_grid_test(void) { return max_grid() == kMaxGrid ? 0 : int(max_grid()); }
 
 extern "C" int dccl_copy_multi(const void* const* srcs, void* const* dsts, int npairs, size_t bytes, void* stream) {
     if (npairs < 0 || npairs > 8 || (npairs > 0 && (srcs == nullptr || dsts == nullptr))) return DCCL_INVALID_ARGUMENT;
@@ -360,7 +363,8 @@ extern "C" int dccl_copy_multi(const void* const* srcs, void* const* dsts, int n
         }
     const auto st = static_cast<hipStream_t>(stream);
     size_t gx = ceil_div(bytes / 16 + 1, 64);
-    if (gx > (size_t(1) << 20)) gx = size_t(1) << 20;
+    const size_t cap = max_grid() < (size_t(1) << 20) ? max_grid() : size_t(1) << 20;  // rows per pair; they stride
+    if (gx > cap) gx = cap;
     void* args[] = {&cl, &npairs, &bytes};
     return hipLaunchKernel(reinterpret_cast<const void*>(&copy_multi_kernel), dim3(unsigned(gx * size_t(npairs))),
                            dim3(64), args, 0, st) == hipSuccess

@@ -678,7 +678,7 @@ __global__ __launch_bounds__(64) void reduce_chain_unaligned_kernel(SendList sen
 inline int launch(const void* fn, size_t grid, void** args, hipStream_t stream, int block = kBlock,
                   size_t lds_bytes = 0) {
     if (grid == 0) return DCCL_SUCCESS;
-    if (grid > kMaxGrid) grid = kMaxGrid;
+    if (const size_t cap = max_grid(); grid > cap) grid = cap;  // kMaxGrid unless a test clamps it (tile_maps.hpp)
     const hipError_t e =
         hipLaunchKernel(fn, dim3(static_cast<unsigned>(grid)), dim3(block), args, lds_bytes, stream);
     return e == hipSuccess ? DCCL_SUCCESS : DCCL_UNHANDLED_DEVICE_ERROR;

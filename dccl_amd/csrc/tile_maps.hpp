@@ -4,6 +4,7 @@
 #pragma once
 
 #include <cstddef>
+#include <cstdlib>
 
 #if defined(__HIPCC__)
 #define DCCL_TILE_FN __host__ __device__ __forceinline__
@@ -14,6 +15,23 @@
 namespace dccl_amd {
 
 constexpr size_t kMaxGrid = size_t(1) << 24;  // grid-stride beyond this (2^24 x 64 threads)
+
+// DCCL_MAX_GRID_TEST as a grid clamp: a decimal integer that is a multiple of 8 from 8 to kMaxGrid, nothing after
+// it; anything else (null, empty, trailing characters, 0, 4, 12, 100, kMaxGrid + 8) is kMaxGrid.
+inline size_t parse_max_grid(const char* e) {
+    if (e == nullptr || *e < '0' || *e > '9') return kMaxGrid;
+    char* end = nullptr;
+    const unsigned long long x = std::strtoull(e, &end, 10);
+    return (*end == '\0' && x >= 8 && x <= kMaxGrid && x % 8 == 0) ? size_t(x) : kMaxGrid;
+}
+// Test-only clamp of every combine and copy launch: DCCL_MAX_GRID_TEST = G, read once per process, makes launch()
+// (reduce_kernels.hpp) clamp its grid at G blocks instead of kMaxGrid, and dccl_copy_multi / copy_rows_launch at
+// min(2^20, G), so tests/test_gpu_grid_stride_small.py runs every kernel's second and later grid-stride passes
+// with operands of about 312 KiB instead of 16 GiB.  Unset, max_grid() is kMaxGrid.
+inline size_t max_grid() {
+    static const size_t g = parse_max_grid(std::getenv("DCCL_MAX_GRID_TEST"));
+    return g;
+}
 
 // Bijective XCD-aware remap (cdna_hip_programming.md, "XCD swizzle must be bijective"):
 // blocks b and b+8 share an XCD, so give each group {b : b % 8 == x} one contiguous range.
@@ -60,7 +78,7 @@ DCCL_TILE_FN size_t first_tile(size_t b, size_t g) {
 }
 
 // One-wave blocks for nvec 16-B vectors, rounded up to a multiple of 8 and at least 8 (the XCD / group tile
-// maps above need one); kMaxGrid, where launch() clamps it, is a multiple of 8 too.
+// maps above need one); max_grid(), where launch() clamps it, is a multiple of 8 too (kMaxGrid, or the test clamp).
 inline size_t unaligned_grid(size_t nvec) {
     const size_t g = ((nvec + 63) / 64 + 7) / 8 * 8;
     return g == 0 ? 8 : g;

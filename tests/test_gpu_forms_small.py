@@ -153,13 +153,14 @@ def source_offsets(rng, case):
     return [a + b for a, b in zip(lanes, ph)]
 
 
-def run_family(family):
-    """In the child: every case of plan(family) on the GPU; returns (cases run, failures)."""
+def run_cases(cases, rng, check_sources=False):
+    """In a child: every case of a plan on the GPU; returns (cases run, failures, the (form, k, dtype) and the
+    (shape, dtype) pairs met).  tests/test_gpu_grid_stride_small.py runs its k-way and chain plans through it too,
+    with check_sources: every source allocation is compared with a device copy taken before the launch."""
     import torch
 
     import dccl_amd
     torch.cuda.set_device(0)
-    rng = np.random.default_rng(7000 + sorted(FAMILY_KS).index(family))
     ran, bad = 0, []
     pairs_k, pairs_size = set(), set()
     data = {}  # (form, slot / k, shape, dt) -> operands and both references, computed once and left unchanged
@@ -184,12 +185,13 @@ def run_family(family):
             data[key] = (op, sends, r, want)
         return data[key]
 
-    for case in plan(family):
+    for case in cases:
         form, k, dt, n, roff = case["form"], case["k"], case["dt"], case["count"], case["roff"]
         esz = esz_of(dt)
         op, sends, r, want = operands(case)
         holders = [dev_bytes(x, o) for x, o in zip(sends, source_offsets(rng, case))]
         sptrs = [h[1] for h in holders]
+        before = [h[0].clone() for h in holders] if check_sources else []
         own = case["own"]
         if own in ("none", "in_place"):
             td, pd = dev_bytes(r, roff)
@@ -207,12 +209,22 @@ def run_family(family):
         nb = n * esz
         got = whole[roff:roff + nb].copy().view(r.dtype)
         ok = rc == 0 and fp_equal(got, want, dt) and not whole[:roff].any() and not whole[roff + nb:].any()
+        ok = ok and all(torch.equal(h[0], b) for h, b in zip(holders, before))
+        if check_sources and own not in ("none", "in_place"):
+            ok = ok and to.cpu().numpy()[ooff:ooff + nb].tobytes() == r.tobytes()
         if not ok:
             where = np.flatnonzero(got.view(np.uint8) != want.view(np.uint8))[:4].tolist() if rc == 0 else []
             bad.append((case, op, rc, where))
         ran += 1
         pairs_k.add((form, k, dt))
         pairs_size.add((case["shape"], dt))
+    return ran, bad, pairs_k, pairs_size
+
+
+def run_family(family):
+    """In the child: every case of plan(family) on the GPU; returns (cases run, failures)."""
+    rng = np.random.default_rng(7000 + sorted(FAMILY_KS).index(family))
+    ran, bad, pairs_k, pairs_size = run_cases(plan(family), rng)
     # the plan really met every (k, dtype) and (dtype, size) pair
     for form, ks in FAMILY_KS[family].items():
         assert {(form, k, dt) for k in ks for dt in DTS} <= pairs_k, "a (k, dtype) pair is missing"

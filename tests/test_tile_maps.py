@@ -3,7 +3,9 @@ HIP include, so g++ compiles it into a harness that checks every map exhaustivel
 section.  Every kernel's coverage of its tiles rests on these maps being bijections on [0, grid) (kOrderXcd on a
 grid that is a multiple of 8), on tile_order (runtime order) and first_tile (template order) being the same map,
 and on the strided walk `t = first(b); t < ntiles; t += grid` visiting every tile once at the launchers' own grids
-and at the capped grids a grid_cap can produce."""
+and at the capped grids a grid_cap can produce.  The test-only clamp DCCL_MAX_GRID_TEST (max_grid(), where launch()
+clamps every grid) is parsed here, the walks are repeated under it at 8 and 104, and the plan of
+tests/test_gpu_grid_stride_small.py, which runs the kernels under those clamps, is checked without a GPU."""
 import json
 import os
 import subprocess
@@ -74,7 +76,51 @@ static bool covers(Map f, size_t g, size_t ntiles) {
     return visits == ntiles;
 }
 
-int main() {
+// With an argument: the parse of DCCL_MAX_GRID_TEST and the walks at min(the launcher's grid, max_grid()), which
+// is what launch() hands the kernels in a process that carries the variable.
+static int clamped_main() {
+    Section parse{"parse"};
+    const struct { const char* text; size_t want; } cases[] = {
+        {"8", 8}, {"104", 104}, {"16777216", kMaxGrid},
+        {nullptr, kMaxGrid}, {"", kMaxGrid}, {"104x", kMaxGrid}, {"8 ", kMaxGrid}, {" 8", kMaxGrid}, {"+8", kMaxGrid},
+        {"-8", kMaxGrid}, {"0x10", kMaxGrid}, {"0", kMaxGrid}, {"4", kMaxGrid}, {"12", kMaxGrid}, {"100", kMaxGrid},
+        {"16777224", kMaxGrid}, {"99999999999999999999999", kMaxGrid}};
+    for (const auto& c : cases) {
+        const size_t got = parse_max_grid(c.text);
+        if (got != c.want) parse.bad("parse", c.text ? c.text : "(null)", got, c.want, 0);
+        ++parse.n;
+    }
+    const size_t mg = max_grid();
+    Section cov{"clamped_coverage"}, part{"clamped_partial_owner"};
+    for (size_t ntiles = 0; ntiles <= 700; ++ntiles) {
+        const size_t own_any = ntiles ? ntiles : 1, own_8 = unaligned_grid(ntiles * 64);
+        const size_t g_any = own_any < mg ? own_any : mg, g_8 = own_8 < mg ? own_8 : mg;
+        for (int m = 0; m < 5; ++m) {
+            if (!covers(kAnyGrid[m], g_any, ntiles)) cov.bad("coverage", kAnyGridName[m], ntiles, g_any, 0);
+            ++cov.n;
+        }
+        for (int o = 0; o < 5; ++o) {
+            if (!covers(kOrderRt[o], g_8, ntiles)) cov.bad("coverage", "tile_order", size_t(o), ntiles, g_8);
+            if (!covers(kOrderCt[o], g_8, ntiles)) cov.bad("coverage", "first_tile", size_t(o), ntiles, g_8);
+            cov.n += 2;
+        }
+        const size_t nfull = ntiles, own = nfull + 1, g = own < mg ? own : mg;  // reduce_vec_kernel's partial tile
+        for (int m = 0; m < 5; ++m) {
+            int owners = 0;
+            for (size_t b = 0; b < g; ++b) owners += kAnyGrid[m](b, g) == nfull % g;
+            if (owners != 1) part.bad("owners of the partial tile", kAnyGridName[m], nfull, g, size_t(owners));
+            if (!covers(kAnyGrid[m], g, nfull)) part.bad("full tiles", kAnyGridName[m], nfull, g, 0);
+            ++part.n;
+        }
+    }
+    std::printf("{\"max_grid\": %zu, ", mg);
+    parse.print(); cov.print(); part.print(true);
+    std::printf("}\n");
+    return 0;
+}
+
+int main(int argc, char**) {
+    if (argc > 1) return clamped_main();
     std::vector<size_t> grids;
     for (size_t g = 1; g <= 2048; ++g) grids.push_back(g);
     grids.push_back(kMaxGrid);
@@ -182,13 +228,29 @@ int main() {
 
 
 @pytest.fixture(scope="module")
-def verdict(tmp_path_factory):
+def harness(tmp_path_factory):
     d = tmp_path_factory.mktemp("tile_maps")
     src, exe = d / "tile_maps_check.cpp", d / "tile_maps_check"
     src.write_text(HARNESS)
     subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", f"-I{CSRC}", str(src), "-o", str(exe)],
                    check=True)
-    return json.loads(subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=300).stdout)
+    return str(exe)
+
+
+@pytest.fixture(scope="module")
+def verdict(harness):
+    env = {k: v for k, v in os.environ.items() if k != "DCCL_MAX_GRID_TEST"}
+    return json.loads(subprocess.run([harness], check=True, capture_output=True, text=True, timeout=300,
+                                     env=env).stdout)
+
+
+def clamped_verdict(harness, value):
+    """The harness's clamped sections in a process whose DCCL_MAX_GRID_TEST is `value` (None: unset)."""
+    env = {k: v for k, v in os.environ.items() if k != "DCCL_MAX_GRID_TEST"}
+    if value is not None:
+        env["DCCL_MAX_GRID_TEST"] = value
+    return json.loads(subprocess.run([harness, "clamped"], check=True, capture_output=True, text=True, timeout=300,
+                                     env=env).stdout)
 
 
 def _passed(verdict, section, n):
@@ -231,3 +293,33 @@ def test_strided_walk_visits_every_tile_once(verdict):
 def test_vec_kernel_partial_tile_has_one_owner(verdict):
     """reduce_vec_kernel hands the partial last tile to the block with bid == nfull % grid: exactly one."""
     _passed(verdict, "vec_partial_owner", 701 * 6 * 5)
+
+
+KMAXGRID = 1 << 24
+
+
+def test_max_grid_parse(harness):
+    """parse_max_grid accepts 8, 104 and 2^24 and turns everything else into kMaxGrid (null, empty, trailing
+    characters, a sign, a space, 0, 4, 12, 100, kMaxGrid + 8, an overflow); max_grid() reads the environment."""
+    _passed(clamped_verdict(harness, None), "parse", 17)
+    for value, want in ((None, KMAXGRID), ("", KMAXGRID), ("8", 8), ("104", 104), (str(KMAXGRID), KMAXGRID),
+                        ("104x", KMAXGRID), ("0", KMAXGRID), ("4", KMAXGRID), ("12", KMAXGRID), ("100", KMAXGRID),
+                        (str(KMAXGRID + 8), KMAXGRID)):
+        assert clamped_verdict(harness, value)["max_grid"] == want, value
+
+
+@pytest.mark.parametrize("value", [None, "8", "104"])
+def test_strided_walk_under_the_test_clamp(harness, value):
+    """The walks of test_strided_walk_visits_every_tile_once and test_vec_kernel_partial_tile_has_one_owner at
+    min(the launcher's own grid, max_grid()) for ntiles in 0..700: up to 88 passes at 8, up to 7 at 104."""
+    v = clamped_verdict(harness, value)
+    assert v["max_grid"] == (KMAXGRID if value is None else int(value))
+    _passed(v, "clamped_coverage", 701 * (5 + 5 * 2))
+    _passed(v, "clamped_partial_owner", 701 * 5)
+
+
+def test_grid_stride_plan_is_the_stated_product():
+    """tests/test_gpu_grid_stride_small.py without a GPU: every family's plan has the stated number of cases, every
+    planned case at least 2 * 104 + 1 tiles by its count, dtype and destination offset."""
+    from tests import test_gpu_grid_stride_small as stride
+    stride.check_plan()
