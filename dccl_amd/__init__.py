@@ -110,6 +110,9 @@ def _load():
         "dccl_local_scale": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_local_reduce_chain_premul": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                    c_size_t, c_void_p, c_int, c_void_p]),
+        "dccl_local_reduce_chain_wide": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
+                                                 c_size_t, c_void_p]),
+        "dccl_local_convert": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p]),
         "dccl_register_host_memory": (c_int, [c_void_p, c_size_t]),
         "dccl_deregister_host_memory": (c_int, [c_void_p]),
         "dccl_size_of_type": (c_size_t, [c_int]),
@@ -135,6 +138,7 @@ def _load():
         "dccl_all_gather": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
         "dccl_red_op_create_premul_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
         "dccl_red_op_destroy": (c_int, [c_int, c_void_p]),
+        "dccl_red_op_create_wide_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_void_p]),
         "dccl_rccl_available": (c_int, []),
         "dccl_bootstrap_unique_id": (c_int, [ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
         "dccl_bootstrap_done": (c_int, [ctypes.c_uint32, ctypes.c_uint32]),
@@ -170,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "dccl_host_reduce_gpu_min_bytes",
     "dccl_local_scale", "dccl_local_reduce_chain_premul", "dccl_red_op_create_premul_sum", "dccl_red_op_destroy",
     "dccl_copy_rows_multi", "dccl_copy_rows_check", "dccl_group_start", "dccl_group_end", "dccl_group_stats",
+    "dccl_local_reduce_chain_wide", "dccl_local_convert", "dccl_red_op_create_wide_sum",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -268,6 +273,18 @@ def local_reduce_chain_premul(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int,
     arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
     return int(lib.dccl_local_reduce_chain_premul(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
                                                   scalar_ptr, int(residence), stream or None))
+
+
+def local_reduce_chain_wide(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, stream: int = 0) -> int:
+    """local_reduce_chain with op Sum for fp16 (6) / bf16 (9), accumulated in fp32 and rounded once (one pass)."""
+    arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
+    return int(lib.dccl_local_reduce_chain_wide(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
+                                                stream or None))
+
+
+def local_convert(src_ptr: int, src_dtype: int, dst_ptr: int, dst_dtype: int, count: int, stream: int = 0) -> int:
+    """fp16 / bf16 -> fp32 (exact) or fp32 -> fp16 / bf16 (round to nearest-even); src and dst share no byte."""
+    return int(lib.dccl_local_convert(src_ptr, int(src_dtype), dst_ptr, int(dst_dtype), int(count), stream or None))
 
 
 def local_reduce_chain_host(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, op: int) -> int:
@@ -407,6 +424,13 @@ class Comm:
         op = ctypes.c_int(-1)
         rc = int(lib.dccl_red_op_create_premul_sum(ctypes.byref(op), scalar_ptr, int(dtype), int(residence),
                                                    self.handle))
+        return rc, int(op.value)
+
+    def red_op_create_wide_sum(self, dtype: int):
+        """dcclRedOpCreateWideSum: returns (rc, op); ``op`` sums fp16 / bf16 contributions in fp32 and rounds once,
+        in all_reduce / reduce_scatter / reduce of this communicator with ``dtype`` and device buffers."""
+        op = ctypes.c_int(-1)
+        rc = int(lib.dccl_red_op_create_wide_sum(ctypes.byref(op), int(dtype), self.handle))
         return rc, int(op.value)
 
     def red_op_destroy(self, op: int) -> int:

@@ -209,6 +209,10 @@ ncclResult_t ensure_pack(dccl::dcclComm* c, size_t bytes) {
     return grow(&c->dev_pack, &c->dev_pack_bytes, bytes, true);
 }
 
+ncclResult_t ensure_wide(dccl::dcclComm* c, size_t bytes) {
+    return grow(&c->dev_wide, &c->dev_wide_bytes, bytes, true);
+}
+
 bool fault_injected(const char* site, uint32_t rank) {
     // read once per process (the tests set it per child process): no getenv on the collectives' steps
     static const std::string spec = [] {

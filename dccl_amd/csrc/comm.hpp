@@ -90,18 +90,23 @@ private:
     std::atomic<uint64_t> barrier_gen_{0};  // written under bmu_, polled without it
 };
 
-// A pre-multiplied-sum op of a communicator (ncclRedOpCreatePreMulSum); handle = ncclNumOps + its slot.
+// A user op of a communicator: a pre-multiplied sum (ncclRedOpCreatePreMulSum) or a wide sum
+// (dcclRedOpCreateWideSum, fp16 / bf16 accumulated in fp32; no scalar); handle = ncclNumOps + its slot.
 constexpr int kMaxUserOps = 16;
+enum UserOpKind : int { kPremulSum = 0, kWideSum = 1 };
 struct UserOp {
     bool live = false;
+    int kind = kPremulSum;
     int dtype = 0;
     uint64_t bits = 0;              // the scalar's bytes, read at creation (ncclScalarHostImmediate)
     const void* dev_ptr = nullptr;  // ncclScalarDevice: read by each collective's kernels when they run
 };
 // What a collective hands down for such an op: dccl_local_scale's (scalar, residence); scalar nullptr = none.
+// `wide`: a wide sum (never together with a scalar): the chain launch becomes dccl_local_reduce_chain_wide.
 struct PremulArg {
     const void* scalar = nullptr;
     int residence = 0;
+    bool wide = false;
 };
 
 }  // namespace dccl_amd
@@ -148,6 +153,10 @@ struct dccl::dcclComm {
     size_t dev_pack_bytes = 0;
     hipEvent_t dev_pack_done = nullptr;  // recorded behind each run's unpack: the next run's pack waits for it
     hipEvent_t dev_pack_join = nullptr;  // joins the other streams of a run to the run's stream, and back
+    // fp32 staging of a wide sum outside the direct paths (dccl_api.cpp).  Its own allocation: the
+    // fp32 reduce-scatter and non-root reduce that run ON it already use dev_work.
+    void* dev_wide = nullptr;
+    size_t dev_wide_bytes = 0;
     dccl_amd::UserOp user_ops[dccl_amd::kMaxUserOps];  // used by the communicator's own thread only
 };
 
@@ -179,6 +188,7 @@ inline ncclResult_t p2p_exchange(dccl::dcclComm* c, const void* sendbuf, size_t 
 ncclResult_t ensure_scratch(dccl::dcclComm* c, size_t bytes, bool device);
 ncclResult_t ensure_work(dccl::dcclComm* c, size_t bytes, bool device);
 ncclResult_t ensure_pack(dccl::dcclComm* c, size_t bytes);  // device memory; dev_pack_bytes changes when it grew
+ncclResult_t ensure_wide(dccl::dcclComm* c, size_t bytes);  // device memory
 
 // dccl_copy_rows_multi's launch without its validation (copy_rows.hip), for plans disjoint by construction.
 int copy_rows_launch(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, hipStream_t stream);

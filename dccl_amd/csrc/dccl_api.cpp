@@ -85,16 +85,21 @@ ncclResult_t copy_bytes(void* dst, const void* src, size_t bytes, bool device, h
     return dccl::ncclSuccess;
 }
 
-// A pre-multiplied-sum handle that is live on `c` becomes (ncclSum, its scalar); every other op value keeps
-// today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything else -> ncclInvalidArgument).
+// A pre-multiplied-sum handle that is live on `c` becomes (ncclSum, its scalar), a wide-sum handle (ncclSum, the
+// wide flag); every other op value keeps today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything
+// else -> ncclInvalidArgument).
 ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, PremulArg* pm) {
     const int slot = *op - int(dccl::ncclNumOps);
     if (slot < 0 || slot >= kMaxUserOps || !c->user_ops[slot].live) return check_op_dtype(dtype, *op);
     const UserOp& u = c->user_ops[slot];
     if (u.dtype != dtype) return dccl::ncclInvalidArgument;
+    *op = dccl::ncclSum;
+    if (u.kind == kWideSum) {  // (ncclSum, wide flag): no scalar
+        pm->wide = true;
+        return dccl::ncclSuccess;
+    }
     pm->scalar = u.dev_ptr != nullptr ? u.dev_ptr : static_cast<const void*>(&u.bits);
     pm->residence = u.dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate;
-    *op = dccl::ncclSum;
     return dccl::ncclSuccess;
 }
 
@@ -401,6 +406,7 @@ ncclResult_t ncclCommFinalize(ncclComm_t comm) {
     if (comm->dev_scratch) (void)hipFree(comm->dev_scratch);
     if (comm->dev_work) (void)hipFree(comm->dev_work);
     if (comm->dev_pack) (void)hipFree(comm->dev_pack);
+    if (comm->dev_wide) (void)hipFree(comm->dev_wide);
     if (comm->dev_pack_done) (void)hipEventDestroy(comm->dev_pack_done);
     if (comm->dev_pack_join) (void)hipEventDestroy(comm->dev_pack_join);
     for (void* h : {comm->host_scratch, comm->host_work}) {
@@ -483,7 +489,7 @@ ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncc
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
-    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;  // the scaling runs on the GPU only
+    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;  // scaling / widening run on the GPU only
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;  // e.g. host buffers on RCCL / IPC
     const uint32_t W = comm->world;
     const Algorithm algo = allreduce_algorithm();  // dccl.cpp:412-413,454
@@ -507,6 +513,8 @@ bool runs_rabenseifner(const Call& c) {
     return true;
 }
 
+ncclResult_t wide_staged(const Call& c, hipStream_t stream);  // below: a wide sum outside the direct paths
+
 ncclResult_t ar_run(const Call& c, hipStream_t stream) {
     const ncclComm_t comm = c.comm;
     const void* sendbuff = c.send;
@@ -523,6 +531,7 @@ ncclResult_t ar_run(const Call& c, hipStream_t stream) {
         return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, &pm);
     if (W > 1 && !dev && host_direct_selected(comm, total / W))
         return direct_all_reduce_host(comm, sendbuff, recvbuff, count, datatype, op);
+    if (pm.wide) return wide_staged(c, stream);
     if (W > 1 && algo != Algorithm::kRabenseifner && pm.scalar == nullptr && grouped_selected(comm, dev))
         return all_reduce_grouped(comm, sendbuff, recvbuff, count, datatype, op, stream);
     rc = stage_input(recvbuff, sendbuff, count, datatype, pm, dev, stream);  // dccl.cpp:393-408
@@ -549,7 +558,7 @@ ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount,
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
-    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
+    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
     *c = Call{group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype, user_op, op, pm, 0, 0, dev,
               Algorithm::kRing, nullptr};
@@ -572,6 +581,7 @@ ncclResult_t rs_run(const Call& c, hipStream_t stream) {
         return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream, &pm);
     if (W > 1 && !dev && host_direct_selected(comm, slot))
         return direct_reduce_scatter_host(comm, sendbuff, recvbuff, recvcount, datatype, op);
+    if (pm.wide) return wide_staged(c, stream);
     // slot r, reduced straight from sendbuff: no work copy (a pre-multiplied sum scales into the work copy: the ring)
     if (W > 1 && pm.scalar == nullptr && grouped_selected(comm, dev))
         return reduce_scatter_grouped(comm, sendbuff, recvbuff, recvcount * W, datatype, op, stream, 0);
@@ -606,7 +616,7 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
     if (sendbuff == nullptr || (iamroot && recvbuff == nullptr)) return ncclInvalidArgument;
     bool dev = false;
     if ((rc = placement(sendbuff, iamroot ? recvbuff : sendbuff, &dev)) != ncclSuccess) return rc;
-    if (pm.scalar != nullptr && !dev) return ncclInvalidUsage;
+    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;
     if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
     *c = Call{group::kReduce, comm, sendbuff, recvbuff, count, datatype, user_op, op, pm, 0, root, dev,
               Algorithm::kRing, nullptr};
@@ -627,6 +637,7 @@ ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
     const bool iamroot = r == uint32_t(root);
     if (W > 1 && dev && direct_selected(comm))
         return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, &pm);
+    if (pm.wide) return wide_staged(c, stream);
     const size_t total = count * size_of_dtype(datatype), slot = total / W;
     void* rbuf = recvbuff;
     if (!iamroot) {
@@ -753,6 +764,35 @@ ncclResult_t run_plain(const Call& c) {
     case group::kAllGather: return ag_run(c, c.stream);
     default: return bcast_run(c, c.stream);
     }
+}
+
+// A wide sum (dcclRedOpCreateWideSum) on every path but the direct ones: widen the input into the communicator's
+// fp32 staging buffer, run the ncclFloat32 / ncclSum collective these settings select on it (ring, Rabenseifner,
+// p2p, RCCL ring or grouped), and round its result once into recvbuff (ncclReduce: on the root only).  A
+// reduce-scatter's fp32 result lies behind the widened input.  The staging buffer is not dev_work: rs_run and
+// reduce_run grow that one underneath.  W == 1: the input's bytes.
+ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
+    dcclComm* comm = c.comm;
+    const uint32_t W = comm->world;
+    const bool rs = c.api == group::kReduceScatter;
+    const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
+    const bool has_out = c.api != group::kReduce || comm->rank == uint32_t(c.root);
+    if (W == 1) return copy_bytes(c.recv, c.send, out_count * size_of_dtype(c.dtype), true, stream);
+    ncclResult_t rc = ensure_wide(comm, (in_count + (rs ? out_count : 0)) * sizeof(float));
+    if (rc != ncclSuccess) return rc;
+    float* wide = static_cast<float*>(comm->dev_wide);
+    rc = static_cast<ncclResult_t>(dccl_local_convert(c.send, c.dtype, wide, ncclFloat32, in_count, stream));
+    if (rc != ncclSuccess) return rc;
+    Call f = c;
+    f.send = wide;
+    f.recv = rs ? wide + in_count : wide;
+    f.dtype = ncclFloat32;
+    f.op = ncclSum;
+    f.pm = PremulArg{};
+    f.stream = stream;
+    rc = run_plain(f);
+    if (rc != ncclSuccess || !has_out) return rc;
+    return static_cast<ncclResult_t>(dccl_local_convert(f.recv, ncclFloat32, c.recv, c.dtype, out_count, stream));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -971,6 +1011,23 @@ ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataTyp
     return ncclInvalidUsage;  // kMaxUserOps live ops already
 }
 
+ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    if (op == nullptr) return ncclInvalidArgument;
+    if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
+    for (int slot = 0; slot < kMaxUserOps; ++slot) {
+        UserOp& u = comm->user_ops[slot];
+        if (u.live) continue;
+        u = UserOp{};
+        u.live = true;
+        u.kind = kWideSum;
+        u.dtype = datatype;
+        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
+        return ncclSuccess;
+    }
+    return ncclInvalidUsage;  // kMaxUserOps live ops already
+}
+
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
     validate_comm(comm, __func__);
     const int slot = int(op) - int(ncclNumOps);
@@ -1131,6 +1188,16 @@ extern "C" int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dt
         const ncclResult_t rc = dccl::ncclRedOpCreatePreMulSum(
             op != nullptr ? &h : nullptr, const_cast<void*>(scalar), static_cast<dccl::ncclDataType_t>(dtype),
             static_cast<dccl::ncclScalarResidence_t>(residence), static_cast<dccl::ncclComm_t>(comm));
+        if (rc == dccl::ncclSuccess) *op = int(h);
+        return rc;
+    });
+}
+
+extern "C" int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm) {
+    return guarded([&] {
+        dccl::ncclRedOp_t h = dccl::ncclSum;
+        const ncclResult_t rc = dccl::dcclRedOpCreateWideSum(
+            op != nullptr ? &h : nullptr, static_cast<dccl::ncclDataType_t>(dtype), static_cast<dccl::ncclComm_t>(comm));
         if (rc == dccl::ncclSuccess) *op = int(h);
         return rc;
     });

@@ -633,6 +633,10 @@ ncclResult_t chain(const Peers& P, uint32_t W, uint32_t first, size_t off, const
     if (pm != nullptr && pm->scalar != nullptr)
         return static_cast<ncclResult_t>(dccl_local_reduce_chain_premul(
             sends, int(W - 1), own, dst, dtype, elems, pm->scalar, pm->residence, static_cast<void*>(st)));
+    // `pm` wide: a wide sum (fp16 / bf16, op is ncclSum), the same chain accumulated in fp32 and rounded once
+    if (pm != nullptr && pm->wide)
+        return static_cast<ncclResult_t>(
+            dccl_local_reduce_chain_wide(sends, int(W - 1), own, dst, dtype, elems, static_cast<void*>(st)));
     return static_cast<ncclResult_t>(
         dccl_local_reduce_chain(sends, int(W - 1), own, dst, dtype, elems, op, static_cast<void*>(st)));
 }

@@ -105,6 +105,19 @@ ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataTyp
                                       ncclScalarResidence_t residence, ncclComm_t comm);
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
 
+/** Wide sum (no NCCL counterpart as an op; NCCL's peer-memory kernels accumulate this way): `*op` becomes a handle
+ *  from the same table as the pre-multiplied sums (ncclNumOps + slot, 16 live ops per communicator together;
+ *  ncclRedOpDestroy releases it) that ncclAllReduce / ncclReduceScatter / ncclReduce accept on `comm` with
+ *  `datatype` (ncclFloat16 or ncclBfloat16 only) and device buffers.  Every element's W contributions are widened
+ *  to fp32, added in fp32 in the order the algorithm combines them, and rounded to 16 bits ONCE; the results are
+ *  the bits of widening every rank's input to fp32, running the ncclFloat32 / ncclSum collective this communicator
+ *  and these settings would run, and rounding its result to nearest-even.  ncclSum on these datatypes is
+ *  unchanged (it rounds after every combine step).  The direct collectives move the 16-bit bytes they move for
+ *  ncclSum; every other path stages through an fp32 buffer of the communicator.  NULL `op` or
+ *  another datatype: ncclInvalidArgument; a 17th live op: ncclInvalidUsage; host buffers: ncclInvalidUsage.
+ *  A wide sum cannot be combined with a pre-multiplied scalar. */
+ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, ncclComm_t comm);
+
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,

@@ -91,6 +91,20 @@
  *   dccl_group_stats      process-wide counters, in this order: outermost groups ended, calls queued, collectives
  *                         actually issued by group ends, coalesced runs, tensors coalesced, bytes packed.  Fills
  *                         min(n, count) values; returns count.
+ *   dccl_red_op_create_wide_sum  dcclRedOpCreateWideSum: a reduction op for dtype 6 (fp16) or 9 (bf16) that widens
+ *                         every contribution to fp32, adds in fp32 in the algorithm's order and rounds to 16 bits
+ *                         once (the built-in Sum rounds after every combine step and is unchanged).  Results are
+ *                         bit-identical to widening each rank's input, running the fp32 Sum collective of this
+ *                         communicator and these settings, and rounding its result to nearest-even.  The handle
+ *                         comes from the same table as the pre-multiplied sums (5..20, 16 live ops together) and
+ *                         follows their rules: valid in dccl_all_reduce / dccl_reduce_scatter / dccl_reduce on
+ *                         that communicator with the same dtype and DEVICE buffers (host buffers 5, another dtype
+ *                         or a dead handle 4), released by dccl_red_op_destroy.  Create: NULL op 4; a dtype
+ *                         other than 6 / 9 4; a 17th live op 5.  The direct collectives (in-process default,
+ *                         IPC) fuse it into their one chain launch and move the 16-bit bytes; ring,
+ *                         Rabenseifner, plugged-in p2p and RCCL paths widen into an fp32 buffer of the
+ *                         communicator, run the fp32 Sum collective there and narrow into recv.  There is no
+ *                         combination with a pre-multiplied scalar.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -121,6 +135,7 @@ int dccl_reduce(const void* send, void* recv, size_t count, int dtype, int op, i
 int dccl_broadcast(const void* send, void* recv, size_t count, int dtype, int root, void* comm, void* stream);
 int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
 int dccl_red_op_destroy(int op, void* comm);
+int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm);
 int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);

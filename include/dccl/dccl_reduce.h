@@ -106,6 +106,31 @@ int dccl_local_reduce_chain_premul(const void* const* sends, int nsend, const vo
                                    size_t count, const void* scalar, int residence, void* stream);
 
 /*
+ * Wide sum (the device half of dcclRedOpCreateWideSum, include/dccl/dccl.hpp): fp16 (6) / bf16 (9) contributions
+ * accumulated in fp32 and rounded to 16 bits once, instead of once per combine step.
+ *   dccl_local_reduce_chain_wide   dccl_local_reduce_chain's roles, limits (1 <= nsend <= 8) and aliasing rule:
+ *                                  acc = widen(sends[0][i]); acc = widen(sends[j][i]) + acc for j = 1..nsend-1;
+ *                                  acc = widen(own[i]) + acc; dst[i] = round16(acc).  widen is exact, every add
+ *                                  one IEEE fp32 add, round16 the nearest-even rounding of the Sum combine: the
+ *                                  bits of widening every operand, running the fp32 Sum chain and rounding
+ *                                  once.  With nsend == 1 that equals dccl_local_reduce_chain with op Sum.
+ *   dccl_local_convert             dst[i] = widen(src[i]) for (src_dtype, dst_dtype) = (6, 7) or (9, 7),
+ *                                  dst[i] = round16(src[i]) for (7, 6) or (7, 9); any other pair 4.
+ * NaN payloads are unpinned, as everywhere.  There is no pre-multiplied form of the wide sum.
+ * Validation, in this order: dtype not 6 / 9 (convert: an unsupported pair) 4, unknown dtypes included; nsend
+ * outside 1..8 or NULL sends 4; count == 0 succeeds; NULL operand 4; chain: an operand partially overlapping dst
+ * 4 (own == dst and a source == dst are allowed); convert: src and dst sharing ANY byte 4 (their element sizes
+ * differ, so there is no in-place form); launch failure 1.
+ * Chain operands that are element-aligned and share dst's 16-byte phase take a 16-byte vector kernel under
+ * the plain chain's caps; the conversion takes its vector kernel (16 B of 16-bit elements against 2 x 16 B of
+ * fp32) when the 16-bit side's vectors and the fp32 side line up on 16-byte boundaries.  Any other placement
+ * (operands off element alignment included) takes an element-wise kernel kept for correctness.
+ */
+int dccl_local_reduce_chain_wide(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
+                                 size_t count, void* stream);
+int dccl_local_convert(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count, void* stream);
+
+/*
  * Multi-source device copy: dsts[y][0..bytes) = srcs[y][0..bytes) for y < npairs (<= 8), in one
  * launch, so the reads of several peers' chunks use several xGMI links at once (the all-gather
  * half of the direct collectives; replaces W-1 ring all-gather steps,

@@ -71,6 +71,27 @@ static void cpu_checks(void) {
     int premul_op = 0;
     CHECK(dccl_red_op_create_premul_sum(&premul_op, &half, 7, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null comm */
     CHECK(dccl_red_op_destroy(5, NULL) == DCCL_INVALID_ARGUMENT);
+    /* wide sum: dtype (fp16 / bf16 only), nsend, count 0, NULL operands, overlap, in that order */
+    CHECK(dccl_local_reduce_chain_wide(sends, 1, a, b, 7, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(sends, 1, a, b, 10, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(sends, 9, a, b, 9, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(NULL, 1, a, b, 6, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(sends, 1, NULL, NULL, 9, 0, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_reduce_chain_wide(sends, 1, NULL, b, 9, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(ov, 1, a, c, 9, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide(sends, 1, c + 1, c, 6, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    /* conversion: the four pairs only, count 0, NULL operands, any shared byte */
+    CHECK(dccl_local_convert(a, 7, b, 7, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(a, 6, b, 9, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(a, 8, b, 7, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(a, 10, b, 7, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(NULL, 9, NULL, 7, 0, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_convert(NULL, 7, b, 6, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(a, 7, NULL, 9, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert(c, 9, c, 7, 4, NULL) == DCCL_INVALID_ARGUMENT);     /* no in-place form */
+    CHECK(dccl_local_convert(c + 1, 7, c, 6, 4, NULL) == DCCL_INVALID_ARGUMENT); /* dst's second half in src */
+    int wide_op = 0;
+    CHECK(dccl_red_op_create_wide_sum(&wide_op, 9, NULL) == DCCL_INVALID_ARGUMENT); /* null communicator */
     /* batched row copy: every validation case answers before any device work (never-dereferenced addresses) */
     {
         char* const base = (char*)(uintptr_t)0x100000000000ull;
