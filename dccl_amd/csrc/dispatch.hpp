@@ -59,6 +59,18 @@ inline bool sources_overlap_destination(const void* const* sends, int nsend, con
     return own != nullptr && partial_overlap(own, dst, bytes);
 }
 
+// The operand checks of every chain and k-way entry point, in their order, after the entry point's own dtype /
+// op / scalar checks: DCCL_INVALID_ARGUMENT, or DCCL_SUCCESS, which with bytes == 0 means "nothing to do"
+// (null operands are then allowed).  The k-way combine passes its destination as `own`.
+inline int check_chain_args(const void* const* sends, int nsend, const void* own, const void* dst, size_t bytes) {
+    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
+    if (bytes == 0) return DCCL_SUCCESS;
+    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
+    for (int k = 0; k < nsend; ++k)
+        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
+    return sources_overlap_destination(sends, nsend, own, dst, bytes) ? DCCL_INVALID_ARGUMENT : DCCL_SUCCESS;
+}
+
 // Test-only scale of the operand size every launcher hands to caps:: (caps.hpp): DCCL_CAPS_TEST_SHIFT = s, an
 // integer 0..12 read once per process (anything else, or unset: 0), makes an operand of `bytes` select the forms
 // of one of bytes << s, so tests/test_gpu_forms_small.py reaches the forms that start at 24, 48 and 96 MiB per

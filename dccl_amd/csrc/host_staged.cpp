@@ -463,18 +463,13 @@ extern "C" int dccl_local_reduce_chain_host(const void* const* sends, int nsend,
                                             int dtype, size_t count, int op) {
     const int v = validate(dtype, op);
     if (v != DCCL_SUCCESS) return v;
-    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (count == 0) return DCCL_SUCCESS;
-    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
-    for (int k = 0; k < nsend; ++k)
-        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (sources_overlap_destination(sends, nsend, own, dst, count * size_of_dtype(dtype)))
-        return DCCL_INVALID_ARGUMENT;
+    int rc = check_chain_args(sends, nsend, own, dst, count * size_of_dtype(dtype));
+    if (rc != DCCL_SUCCESS || count == 0) return rc;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return DCCL_UNHANDLED_DEVICE_ERROR;
     Stager* st = t_stagers.get(dev);
     if (st == nullptr) return DCCL_UNHANDLED_DEVICE_ERROR;
-    int rc = st->init();
+    rc = st->init();
     if (rc != DCCL_SUCCESS) return rc;
     rc = st->run_chain(sends, nsend, own, dst, dtype, count, op);
     (void)hipSetDevice(dev);

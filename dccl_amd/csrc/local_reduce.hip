@@ -32,9 +32,7 @@
 namespace dccl_amd {
 namespace {
 
-// Default configuration of the shipped kernel.  One-wave blocks, one 16-B vector per lane and operand, every access non-temporal: the
-// fastest shape measured on MI355X at 1 GiB (tune_reduce.py@4f20423, profiles/r1_tune.json).
-using DefaultCfg = VecCfg<64, 1, kNtSend | kNtRecv | kNtStore, false>;
+// DefaultCfg, the shipped kernel's configuration: reduce_kernels.hpp.
 // When send's 128-B phase differs from recv's, every 1 KiB send tile straddles 9 lines, one of them
 // shared with the next tile (a wave on another XCD): send is then loaded through the caches, so the
 // shared line is fetched from HBM once (phase_probe.py@4f20423 on MI355X, 1 GiB fp32 Sum: 81.0 % with
@@ -54,8 +52,8 @@ constexpr int kShiftRun = 8;
 size_t recv_align() {
     static const size_t v = [] {
         const char* e = std::getenv("DCCL_REDUCE_ALIGN");
-        const unsigned long long x = e ? std::strtoull(e, nullptr, 10) : 128ull;
-        return (x >= 16 && x <= 4096 && (x & (x - 1)) == 0) ? static_cast<size_t>(x) : size_t(128);
+        const unsigned long long x = e ? std::strtoull(e, nullptr, 10) : kDstAlign;
+        return (x >= 16 && x <= 4096 && (x & (x - 1)) == 0) ? static_cast<size_t>(x) : kDstAlign;
     }();
     return v;
 }
@@ -116,8 +114,7 @@ inline bool any_straddles(const SendList& sl, int nsend, size_t off) {
 template <typename T, int OP, int K>
 int launch_multi_vec(SendList sl, unsigned char* r, Split sp, hipStream_t stream) {
     using C = DefaultCfg;
-    size_t grid = ceil_div(sp.nvec, C::TILE);
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    const size_t grid = grid_for(sp, C::TILE);
     void* args[] = {&sl, &r, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
                   caps::lds(caps::kMulti, K, caps_bytes(sp.nvec * 16)));
@@ -199,8 +196,7 @@ template <typename T, int OP, int K>
 int launch_chain_vec(SendList sl, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream,
                      size_t grid_cap) {
     using C = DefaultCfg;
-    size_t grid = ceil_div(sp.nvec, C::TILE);
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    size_t grid = grid_for(sp, C::TILE);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
@@ -304,13 +300,8 @@ extern "C" int dccl_local_reduce_multi(const void* const* sends, int nsend, void
                                        int op, void* stream) {
     const int v = validate(dtype, op);
     if (v != DCCL_SUCCESS) return v;
-    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (count == 0) return DCCL_SUCCESS;
-    if (recv == nullptr) return DCCL_INVALID_ARGUMENT;
-    for (int k = 0; k < nsend; ++k)
-        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (sources_overlap_destination(sends, nsend, nullptr, recv, count * size_of_dtype(dtype)))
-        return DCCL_INVALID_ARGUMENT;
+    const int rc = check_chain_args(sends, nsend, recv, recv, count * size_of_dtype(dtype));
+    if (rc != DCCL_SUCCESS || count == 0) return rc;
     return dispatch<ReduceMultiFn>(dtype, op, sends, nsend, recv, count, static_cast<hipStream_t>(stream));
 }
 
@@ -321,13 +312,8 @@ __attribute__((visibility("hidden"))) int local_reduce_chain_capped(const void* 
                               size_t count, int op, hipStream_t stream, size_t grid_cap) {
     const int v = validate(dtype, op);
     if (v != DCCL_SUCCESS) return v;
-    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (count == 0) return DCCL_SUCCESS;
-    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
-    for (int k = 0; k < nsend; ++k)
-        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (sources_overlap_destination(sends, nsend, own, dst, count * size_of_dtype(dtype)))
-        return DCCL_INVALID_ARGUMENT;
+    const int rc = check_chain_args(sends, nsend, own, dst, count * size_of_dtype(dtype));
+    if (rc != DCCL_SUCCESS || count == 0) return rc;
     return dispatch<ReduceChainFn>(dtype, op, sends, nsend, own, dst, count, stream, grid_cap / 8 * 8);
 }
 }  // namespace dccl_amd

@@ -13,8 +13,7 @@ namespace {
 
 template <typename T, int OP, int K>
 int launch_phased(SendList sl, PhaseList ph, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream) {
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    const size_t grid = grid_for(sp, 64);
     void* args[] = {&sl, &ph, &own, &d, &sp.head, &sp.nvec, &sp.tail};
     // the per-operand form uncapped (with the XCD order up to kPhasedXcdMaxK), or the loads-first form under
     // its own cap (caps::kChainPhasedFirst, caps.hpp)
@@ -29,8 +28,7 @@ using StraddleKwayCfg = VecCfg<64, 1, kNtRecv | kNtStore, false>;
 
 template <typename T, int OP, int K>
 int launch_straddle(SendList sl, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream) {
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    const size_t grid = grid_for(sp, 64);
     void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
     // the chain kernel's line-straddle caps by operand size (caps::kChainStraddle, caps.hpp)
     return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, StraddleKwayCfg>), grid, args, stream, 64,

@@ -13,8 +13,7 @@ namespace {
 
 template <typename T, int OP, int K>
 int launch_phased(SendList sl, PhaseList ph, unsigned char* r, Split sp, hipStream_t stream) {
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    const size_t grid = grid_for(sp, 64);
     void* args[] = {&sl, &ph, &r, &sp.head, &sp.nvec, &sp.tail};
     // the per-operand form uncapped (with the XCD order up to kPhasedXcdMaxK), or the loads-first form under
     // its own cap (caps::kMultiPhasedFirst, caps.hpp)
@@ -31,8 +30,7 @@ using StraddleKwayCfg = VecCfg<64, 1, kNtRecv | kNtStore, false, 0, caps::tile_r
 
 template <typename T, int OP, int K>
 int launch_straddle(SendList sl, unsigned char* r, Split sp, hipStream_t stream) {
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    const size_t grid = grid_for(sp, 64);
     void* args[] = {&sl, &r, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, StraddleKwayCfg<K>>), grid, args, stream, 64,
                   caps::lds(caps::kMultiStraddle, K, caps_bytes(sp.nvec * 16)));

@@ -17,26 +17,20 @@
 // memory when it runs (stream-ordered, so a captured graph replays with the value of the moment); otherwise
 // `bits` holds the value the host read at the call.  Every store is an ordinary vector store.
 //
-// Forms: operands that are element-aligned and share the destination's 16-B phase take the vector kernels
-// (head scalars | 16-B non-temporal vectors | tail scalars; the chain under local_reduce.hip's chain caps).
-// Any other placement (another phase, operands off element alignment) takes one coalesced element-wise
-// kernel: that fallback is for correctness only, nobody has tuned it.
+// The chain kernels are reduce_kernels.hpp's chain bodies (the plain chain's tile loop, loads, ring order and edge
+// elements) with the PremulChain policy below; their placement rule and launch are chain_forms.hpp's.  The scale
+// follows the same rule with a body of its own: element-aligned operands in one 16-B phase take the vector kernel,
+// any other placement one coalesced element-wise kernel (correctness only, nobody has tuned it).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
+#include "chain_forms.hpp"
 #include "dccl/dccl_reduce.h"
-#include "dispatch.hpp"
-#include "reduce_kernels.hpp"
 
 namespace dccl_amd {
 namespace {
-
-// local_reduce.hip's shipped shape: one-wave blocks, one 16-B vector per lane and operand, all non-temporal
-using DefaultCfg = VecCfg<64, 1, kNtSend | kNtRecv | kNtStore, false>;
-// the head scalars bring the destination to its 128-B lines (local_reduce.hip's default recv_align)
-constexpr size_t kDstAlign = 128;
 
 struct ScalarArg {
     uint64_t bits;        // the scalar's bytes (host-immediate residence)
@@ -91,11 +85,20 @@ __device__ __forceinline__ u32x4 premul16(u32x4 v, T s) {
     return __builtin_bit_cast(u32x4, p);
 }
 
-// index of block 0's j-th scalar element: head [0, head), then the tail past the vector body
+// The chain policy (reduce_kernels.hpp chain_vec_body): every operand is multiplied by s as it enters the Sum.
 template <typename T>
-__device__ __forceinline__ size_t edge_index(size_t j, size_t head, size_t nvec) {
-    return j < head ? j : head + nvec * Pack<T>::N + (j - head);
-}
+struct PremulChain {
+    using Elem = T;
+    T s;
+    __device__ __forceinline__ u32x4 first16(u32x4 v) const { return premul16<T>(v, s); }
+    __device__ __forceinline__ u32x4 fold16(u32x4 v, u32x4 acc) const {
+        return combine16<T, kSum>(premul16<T>(v, s), acc);
+    }
+    __device__ __forceinline__ u32x4 finish16(u32x4 acc) const { return acc; }
+    __device__ __forceinline__ T first(T x) const { return PreMul<T>::apply(x, s); }
+    __device__ __forceinline__ T fold(T x, T acc) const { return Combine<T, kSum>::apply(PreMul<T>::apply(x, s), acc); }
+    __device__ __forceinline__ T finish(T acc) const { return acc; }
+};
 
 // ---- scale ----
 template <typename T>
@@ -129,48 +132,14 @@ template <typename T, int K, typename C>
 __global__ __launch_bounds__(C::BLOCK) void premul_chain_vec_kernel(SendList sends, const unsigned char* own,
                                                                     unsigned char* dst, size_t head, size_t nvec,
                                                                     size_t tail, ScalarArg sa) {
-    static_assert(C::UNROLL == 1, "one vector per lane");
-    const T sc = load_scalar<T>(sa);
-    const size_t off = head * sizeof(T);
-    const u32x4* vo = reinterpret_cast<const u32x4*>(own + off);
-    u32x4* vd = reinterpret_cast<u32x4*>(dst + off);
-    const size_t ntiles = (nvec + C::TILE - 1) / C::TILE;
-    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const size_t i = t * C::TILE + threadIdx.x;
-        if (i < nvec) {
-            u32x4 s[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-                s[k] = ld16<(C::POLICY & kNtSend) != 0>(reinterpret_cast<const u32x4*>(sends.p[k] + off) + i);
-            const u32x4 o = ld16<true>(vo + i);
-            u32x4 acc = premul16<T>(s[0], sc);
-#pragma unroll
-            for (int k = 1; k < K; ++k) acc = combine16<T, kSum>(premul16<T>(s[k], sc), acc);
-            __builtin_nontemporal_store(combine16<T, kSum>(premul16<T>(o, sc), acc), vd + i);
-        }
-    }
-    if (blockIdx.x == 0)
-        for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-            const size_t i = edge_index<T>(j, head, nvec);
-            T acc = PreMul<T>::apply(ld_elem<T, true>(sends.p[0], i), sc);
-#pragma unroll
-            for (int k = 1; k < K; ++k)
-                acc = Combine<T, kSum>::apply(PreMul<T>::apply(ld_elem<T, true>(sends.p[k], i), sc), acc);
-            st_elem<T, true>(dst, i, Combine<T, kSum>::apply(PreMul<T>::apply(ld_elem<T, true>(own, i), sc), acc));
-        }
+    chain_vec_body<PremulChain<T>, K, C>(sends, own, dst, head, nvec, tail, PremulChain<T>{load_scalar<T>(sa)});
 }
 
 // Any placement, one element per thread and step (correctness only).
 template <typename T, bool ALIGNED>
 __global__ __launch_bounds__(kBlock) void premul_chain_elem_kernel(SendList sends, int nsend, const unsigned char* own,
                                                                    unsigned char* dst, size_t count, ScalarArg sa) {
-    const T sc = load_scalar<T>(sa);
-    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < count; i += size_t(gridDim.x) * kBlock) {
-        T acc = PreMul<T>::apply(ld_elem<T, ALIGNED>(sends.p[0], i), sc);
-        for (int k = 1; k < nsend; ++k)
-            acc = Combine<T, kSum>::apply(PreMul<T>::apply(ld_elem<T, ALIGNED>(sends.p[k], i), sc), acc);
-        st_elem<T, ALIGNED>(dst, i, Combine<T, kSum>::apply(PreMul<T>::apply(ld_elem<T, ALIGNED>(own, i), sc), acc));
-    }
+    chain_elem_body<PremulChain<T>, ALIGNED>(sends, nsend, own, dst, count, PremulChain<T>{load_scalar<T>(sa)});
 }
 
 // ---- launches ----
@@ -187,47 +156,16 @@ int scale_typed(const void* src, void* dst, size_t count, ScalarArg sa, hipStrea
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
     Split sp = split_for_vectors<T>(ad, count, kDstAlign);
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
     void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail, &sa};
-    return launch(reinterpret_cast<const void*>(&scale_vec_kernel<T>), grid, args, stream, 64);
+    return launch(reinterpret_cast<const void*>(&scale_vec_kernel<T>), grid_for(sp, 64), args, stream, 64);
 }
 
-template <typename T, int K>
-int launch_premul_chain_vec(SendList sl, const unsigned char* own, unsigned char* d, Split sp, ScalarArg sa,
-                            hipStream_t stream) {
-    using C = DefaultCfg;
-    size_t grid = ceil_div(sp.nvec, C::TILE);
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
-    void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail, &sa};
-    // the plain chain's caps (launch_chain_vec): not measured for this kernel's heavier arithmetic
-    return launch(reinterpret_cast<const void*>(&premul_chain_vec_kernel<T, K, C>), grid, args, stream, C::BLOCK,
-                  caps::lds(caps::kChain, K, caps_bytes(sp.nvec * 16)));
-}
-
-template <typename T>
-int premul_chain_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count, ScalarArg sa,
-                       hipStream_t stream) {
-    SendList sl{};
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst), ao = reinterpret_cast<uintptr_t>(own);
-    bool elem_ok = ad % sizeof(T) == 0 && ao % sizeof(T) == 0, in_phase = ((ad ^ ao) & 15) == 0;
-    for (int k = 0; k < nsend; ++k) {
-        sl.p[k] = static_cast<const unsigned char*>(sends[k]);
-        const uintptr_t a = reinterpret_cast<uintptr_t>(sends[k]);
-        if (a % sizeof(T)) elem_ok = false;
-        if ((a ^ ad) & 15) in_phase = false;
-    }
-    auto o = static_cast<const unsigned char*>(own);
-    auto d = static_cast<unsigned char*>(dst);
-    if (!elem_ok || !in_phase) {
-        void* args[] = {&sl, &nsend, &o, &d, &count, &sa};
-        const void* fn = elem_ok ? reinterpret_cast<const void*>(&premul_chain_elem_kernel<T, true>)
-                                 : reinterpret_cast<const void*>(&premul_chain_elem_kernel<T, false>);
-        return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
-    }
-    const Split sp = split_for_vectors<T>(ad, count, kDstAlign);
-    return with_k<1, 8>(nsend, [&](auto K) { return launch_premul_chain_vec<T, K.value>(sl, o, d, sp, sa, stream); });
-}
+struct PremulChainKernels {  // chain_forms.hpp launch_chain_form
+    template <typename T, int K>
+    static const void* vec() { return reinterpret_cast<const void*>(&premul_chain_vec_kernel<T, K, DefaultCfg>); }
+    template <typename T, bool ALIGNED>
+    static const void* elem() { return reinterpret_cast<const void*>(&premul_chain_elem_kernel<T, ALIGNED>); }
+};
 
 // dispatch.hpp's dtype switch (its op parameter is unused here: callers pass kSum)
 struct ScaleFn {
@@ -240,7 +178,7 @@ struct PremulChainFn {
     template <typename T, int OP>
     static int run(const void* const* sends, int nsend, const void* own, void* dst, size_t count, ScalarArg sa,
                    hipStream_t stream) {
-        return premul_chain_typed<T>(sends, nsend, own, dst, count, sa, stream);
+        return launch_chain_form<PremulChainKernels, T>(sends, nsend, own, dst, count, stream, sa);
     }
 };
 
@@ -274,14 +212,9 @@ extern "C" int dccl_local_reduce_chain_premul(const void* const* sends, int nsen
                                               int dtype, size_t count, const void* scalar, int residence,
                                               void* stream) {
     if (size_of_dtype(dtype) == 0) return DCCL_INVALID_ARGUMENT;
-    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (!scalar_ok(scalar, residence)) return DCCL_INVALID_ARGUMENT;
-    if (count == 0) return DCCL_SUCCESS;
-    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
-    for (int k = 0; k < nsend; ++k)
-        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (sources_overlap_destination(sends, nsend, own, dst, count * size_of_dtype(dtype)))
-        return DCCL_INVALID_ARGUMENT;
+    if (!scalar_ok(scalar, residence)) return DCCL_INVALID_ARGUMENT;  // the same code as a bad nsend, before count == 0
+    const int rc = check_chain_args(sends, nsend, own, dst, count * size_of_dtype(dtype));
+    if (rc != DCCL_SUCCESS || count == 0) return rc;
     return dispatch<PremulChainFn>(dtype, kSum, sends, nsend, own, dst, count, make_scalar(scalar, residence, dtype),
                                    static_cast<hipStream_t>(stream));
 }

@@ -56,6 +56,17 @@ struct VecCfg {
     static constexpr bool XCD = XCD_;
     static constexpr size_t TILE = size_t(BLOCK_) * UNROLL_;
 };
+// The shipped shape: one-wave blocks, one 16-B vector per lane and operand, every access non-temporal: the
+// fastest shape measured on MI355X at 1 GiB (tune_reduce.py@4f20423, profiles/r1_tune.json).
+using DefaultCfg = VecCfg<64, 1, kNtSend | kNtRecv | kNtStore, false>;
+// The head scalars bring the destination to its 128-B lines (local_reduce.hip's recv_align() may override it).
+constexpr size_t kDstAlign = 128;
+
+// Index of block 0's j-th scalar element: head [0, head), then the tail past the nvec 16-B vectors.
+template <typename T>
+__device__ __forceinline__ size_t edge_index(size_t j, size_t head, size_t nvec) {
+    return j < head ? j : head + nvec * Pack<T>::N + (j - head);
+}
 
 // Block 0's scalar elements outside the vector body: head [0, head) (< the recv alignment) and tail
 // (< one vector).  SEND_ALIGNED false: send is not element-aligned (byte loads of its elements).
@@ -63,7 +74,7 @@ template <typename T, int OP, bool SEND_ALIGNED = true>
 __device__ __forceinline__ void edge_scalars(const unsigned char* send, unsigned char* recv, size_t head,
                                              size_t nvec, size_t tail) {
     for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-        const size_t i = j < head ? j : head + nvec * Pack<T>::N + (j - head);
+        const size_t i = edge_index<T>(j, head, nvec);
         const T a = ld_elem<T, true>(recv, i), b = ld_elem<T, SEND_ALIGNED>(send, i);
         st_elem<T, true>(recv, i, Combine<T, OP>::apply(a, b));
     }
@@ -242,7 +253,7 @@ __global__ __launch_bounds__(C::BLOCK) void reduce_multi_vec_kernel(SendList sen
     }
     if (blockIdx.x == 0) {
         for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-            const size_t i = j < head ? j : head + nvec * Pack<T>::N + (j - head);
+            const size_t i = edge_index<T>(j, head, nvec);
             T acc = ld_elem<T, true>(recv, i);
 #pragma unroll
             for (int k = 0; k < K; ++k) acc = Combine<T, OP>::apply(acc, ld_elem<T, true>(sends.p[k], i));
@@ -258,11 +269,17 @@ __global__ __launch_bounds__(C::BLOCK) void reduce_multi_vec_kernel(SendList sen
 // Every application is op(recv = the next rank's own data, send = the partial that arrived),
 // exactly as reduce_scatter_ring.cpp:84-94 applies it, so results are bit-identical to the ring
 // for every dtype and op (Max/Min NaN and signed-zero selection included).  `own` may alias `dst`.
+//
+// The plain, pre-multiplied (premul.hip) and wide (wide.hip) chains share the two bodies below: the tile
+// loop, the loads, the fold in the ring's order and block 0's head / tail elements are stated once.  A policy
+// E says what one fold is: E::Elem is the stored element type; first16 takes the first operand's 16 bytes
+// into the accumulator, fold16(v, acc) folds a further operand in, finish16 turns the accumulator back into
+// 16 stored bytes; first / fold / finish do the same for one element.
 // ---------------------------------------------------------------------------------
-template <typename T, int OP, int K, typename C>
-__global__ __launch_bounds__(C::BLOCK) void reduce_chain_vec_kernel(SendList sends, const unsigned char* own,
-                                                                    unsigned char* dst, size_t head, size_t nvec,
-                                                                    size_t tail) {
+template <typename E, int K, typename C>
+__device__ __forceinline__ void chain_vec_body(SendList sends, const unsigned char* own, unsigned char* dst,
+                                               size_t head, size_t nvec, size_t tail, E e) {
+    using T = typename E::Elem;
     static_assert(C::UNROLL == 1, "one vector per lane");
     const size_t off = head * sizeof(T);
     const u32x4* vo = reinterpret_cast<const u32x4*>(own + off);
@@ -277,21 +294,52 @@ __global__ __launch_bounds__(C::BLOCK) void reduce_chain_vec_kernel(SendList sen
             for (int k = 0; k < K; ++k)
                 s[k] = ld16<(C::POLICY & kNtSend) != 0>(reinterpret_cast<const u32x4*>(sends.p[k] + off) + i);
             const u32x4 o = ld16<true>(vo + i);
-            u32x4 acc = s[0];
+            auto acc = e.first16(s[0]);
 #pragma unroll
-            for (int k = 1; k < K; ++k) acc = combine16<T, OP>(s[k], acc);
-            __builtin_nontemporal_store(combine16<T, OP>(o, acc), vd + i);
+            for (int k = 1; k < K; ++k) acc = e.fold16(s[k], acc);
+            __builtin_nontemporal_store(e.finish16(e.fold16(o, acc)), vd + i);
         }
     }
     if (blockIdx.x == 0) {
         for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-            const size_t i = j < head ? j : head + nvec * Pack<T>::N + (j - head);
-            T acc = ld_elem<T, true>(sends.p[0], i);
+            const size_t i = edge_index<T>(j, head, nvec);
+            auto acc = e.first(ld_elem<T, true>(sends.p[0], i));
 #pragma unroll
-            for (int k = 1; k < K; ++k) acc = Combine<T, OP>::apply(ld_elem<T, true>(sends.p[k], i), acc);
-            st_elem<T, true>(dst, i, Combine<T, OP>::apply(ld_elem<T, true>(own, i), acc));
+            for (int k = 1; k < K; ++k) acc = e.fold(ld_elem<T, true>(sends.p[k], i), acc);
+            st_elem<T, true>(dst, i, e.finish(e.fold(ld_elem<T, true>(own, i), acc)));
         }
     }
+}
+
+// The same fold at any placement, one element per thread and step: the correctness-only fallback of the
+// pre-multiplied and wide chains (ALIGNED false: operands off element alignment, byte loads and stores).
+template <typename E, bool ALIGNED>
+__device__ __forceinline__ void chain_elem_body(SendList sends, int nsend, const unsigned char* own,
+                                                unsigned char* dst, size_t count, E e) {
+    using T = typename E::Elem;
+    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < count; i += size_t(gridDim.x) * kBlock) {
+        auto acc = e.first(ld_elem<T, ALIGNED>(sends.p[0], i));
+        for (int k = 1; k < nsend; ++k) acc = e.fold(ld_elem<T, ALIGNED>(sends.p[k], i), acc);
+        st_elem<T, ALIGNED>(dst, i, e.finish(e.fold(ld_elem<T, ALIGNED>(own, i), acc)));
+    }
+}
+
+template <typename T, int OP>
+struct PlainChain {
+    using Elem = T;
+    __device__ __forceinline__ u32x4 first16(u32x4 v) const { return v; }
+    __device__ __forceinline__ u32x4 fold16(u32x4 v, u32x4 acc) const { return combine16<T, OP>(v, acc); }
+    __device__ __forceinline__ u32x4 finish16(u32x4 acc) const { return acc; }
+    __device__ __forceinline__ T first(T x) const { return x; }
+    __device__ __forceinline__ T fold(T x, T acc) const { return Combine<T, OP>::apply(x, acc); }
+    __device__ __forceinline__ T finish(T acc) const { return acc; }
+};
+
+template <typename T, int OP, int K, typename C>
+__global__ __launch_bounds__(C::BLOCK) void reduce_chain_vec_kernel(SendList sends, const unsigned char* own,
+                                                                    unsigned char* dst, size_t head, size_t nvec,
+                                                                    size_t tail) {
+    chain_vec_body<PlainChain<T, OP>, K, C>(sends, own, dst, head, nvec, tail, PlainChain<T, OP>{});
 }
 
 // ---------------------------------------------------------------------------------
@@ -426,7 +474,7 @@ __global__ __launch_bounds__(64) void reduce_multi_phased_kernel(SendList sends,
     }
     if (blockIdx.x == 0) {
         for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-            const size_t i = j < head ? j : head + nvec * Pack<T>::N + (j - head);
+            const size_t i = edge_index<T>(j, head, nvec);
             T acc = ld_elem<T, true>(recv, i);
 #pragma unroll
             for (int k = 0; k < K; ++k) acc = Combine<T, OP>::apply(acc, ld_elem<T, false>(sends.p[k], i));
@@ -471,7 +519,7 @@ __global__ __launch_bounds__(64) void reduce_chain_phased_kernel(SendList sends,
     }
     if (blockIdx.x == 0) {
         for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
-            const size_t i = j < head ? j : head + nvec * Pack<T>::N + (j - head);
+            const size_t i = edge_index<T>(j, head, nvec);
             T acc = ld_elem<T, false>(sends.p[0], i);
 #pragma unroll
             for (int k = 1; k < K; ++k) acc = Combine<T, OP>::apply(ld_elem<T, false>(sends.p[k], i), acc);
@@ -717,11 +765,16 @@ inline Split split_for_vectors(uintptr_t recv, size_t count, size_t align = 16) 
     return Split{head, nvec, rest - nvec * V};
 }
 
+// One block per `tile` vectors; a split with no whole vector still needs block 0 for its head / tail elements.
+inline size_t grid_for(Split sp, size_t tile) {
+    const size_t grid = ceil_div(sp.nvec, tile);
+    return grid == 0 && sp.head + sp.tail > 0 ? 1 : grid;
+}
+
 template <typename T, int OP, typename C>
 int launch_vec(const unsigned char* s, unsigned char* r, Split sp, hipStream_t stream, size_t grid_cap = 0,
                size_t lds_bytes = 0) {
-    size_t grid = ceil_div(sp.nvec, C::TILE);
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    size_t grid = grid_for(sp, C::TILE);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&s, &r, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&reduce_vec_kernel<T, OP, C>), grid, args, stream, C::BLOCK,
@@ -735,8 +788,7 @@ int launch_shift(const unsigned char* s, unsigned char* r, size_t count, hipStre
                  size_t lds_bytes = 0, size_t grid_cap = 0) {
     Split sp = split_for_vectors<T>(reinterpret_cast<uintptr_t>(r), count, align);
     unsigned p = unsigned((reinterpret_cast<uintptr_t>(s) + sp.head * sizeof(T)) & 15);
-    size_t grid = ceil_div(sp.nvec, size_t(64));
-    if (grid == 0 && (sp.head + sp.tail) > 0) grid = 1;
+    size_t grid = grid_for(sp, 64);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&s, &r, &sp.head, &sp.nvec, &sp.tail, &p};
     return launch(reinterpret_cast<const void*>(&reduce_shift_kernel<T, OP, POLICY, XCD, TAG, SEND_ALIGNED, RUN>), grid,
