@@ -113,6 +113,9 @@ def _load():
         "dccl_local_reduce_chain_wide": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                  c_size_t, c_void_p]),
         "dccl_local_convert": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p]),
+        "dccl_local_reduce_chain_wide_scaled": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
+                                                        c_size_t, c_void_p, c_int, c_void_p]),
+        "dccl_local_convert_scaled": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_register_host_memory": (c_int, [c_void_p, c_size_t]),
         "dccl_deregister_host_memory": (c_int, [c_void_p]),
         "dccl_size_of_type": (c_size_t, [c_int]),
@@ -139,6 +142,7 @@ def _load():
         "dccl_red_op_create_premul_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
         "dccl_red_op_destroy": (c_int, [c_int, c_void_p]),
         "dccl_red_op_create_wide_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_void_p]),
+        "dccl_red_op_create_wide_scaled_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
         "dccl_rccl_available": (c_int, []),
         "dccl_bootstrap_unique_id": (c_int, [ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
         "dccl_bootstrap_done": (c_int, [ctypes.c_uint32, ctypes.c_uint32]),
@@ -175,6 +179,7 @@ EXPORTED_SYMBOLS = [
     "dccl_local_scale", "dccl_local_reduce_chain_premul", "dccl_red_op_create_premul_sum", "dccl_red_op_destroy",
     "dccl_copy_rows_multi", "dccl_copy_rows_check", "dccl_group_start", "dccl_group_end", "dccl_group_stats",
     "dccl_local_reduce_chain_wide", "dccl_local_convert", "dccl_red_op_create_wide_sum",
+    "dccl_local_reduce_chain_wide_scaled", "dccl_local_convert_scaled", "dccl_red_op_create_wide_scaled_sum",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -285,6 +290,24 @@ def local_reduce_chain_wide(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, c
 def local_convert(src_ptr: int, src_dtype: int, dst_ptr: int, dst_dtype: int, count: int, stream: int = 0) -> int:
     """fp16 / bf16 -> fp32 (exact) or fp32 -> fp16 / bf16 (round to nearest-even); src and dst share no byte."""
     return int(lib.dccl_local_convert(src_ptr, int(src_dtype), dst_ptr, int(dst_dtype), int(count), stream or None))
+
+
+def local_reduce_chain_wide_scaled(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, scalar_ptr: int,
+                                   residence: int, stream: int = 0) -> int:
+    """local_reduce_chain_wide whose fp32 accumulator is multiplied by the scalar before the one rounding.
+    ``scalar_ptr`` addresses ONE float32 whatever ``dtype``: device memory read when the kernel runs (residence 0)
+    or host memory read now (1)."""
+    arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
+    return int(lib.dccl_local_reduce_chain_wide_scaled(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
+                                                       scalar_ptr, int(residence), stream or None))
+
+
+def local_convert_scaled(src_ptr: int, src_dtype: int, dst_ptr: int, dst_dtype: int, count: int, scalar_ptr: int,
+                         residence: int, stream: int = 0) -> int:
+    """dst = round16(as_fp32(src) * scalar): fp32 -> fp16 / bf16 (no shared byte), or fp16 -> fp16 / bf16 -> bf16
+    (src == dst: in place).  The scalar is one float32, as for local_reduce_chain_wide_scaled."""
+    return int(lib.dccl_local_convert_scaled(src_ptr, int(src_dtype), dst_ptr, int(dst_dtype), int(count),
+                                             scalar_ptr, int(residence), stream or None))
 
 
 def local_reduce_chain_host(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, op: int) -> int:
@@ -431,6 +454,15 @@ class Comm:
         in all_reduce / reduce_scatter / reduce of this communicator with ``dtype`` and device buffers."""
         op = ctypes.c_int(-1)
         rc = int(lib.dccl_red_op_create_wide_sum(ctypes.byref(op), int(dtype), self.handle))
+        return rc, int(op.value)
+
+    def red_op_create_wide_scaled_sum(self, scalar_ptr: int, dtype: int, residence: int):
+        """dcclRedOpCreateWideScaledSum: returns (rc, op); ``op`` is the wide sum whose fp32 accumulator is multiplied
+        by the scalar (ONE float32 whatever ``dtype``) before the one rounding, e.g. 1/W for a mean.  Every rank must
+        pass the same scalar value."""
+        op = ctypes.c_int(-1)
+        rc = int(lib.dccl_red_op_create_wide_scaled_sum(ctypes.byref(op), scalar_ptr, int(dtype), int(residence),
+                                                        self.handle))
         return rc, int(op.value)
 
     def red_op_destroy(self, op: int) -> int:

@@ -90,10 +90,11 @@ private:
     std::atomic<uint64_t> barrier_gen_{0};  // written under bmu_, polled without it
 };
 
-// A user op of a communicator: a pre-multiplied sum (ncclRedOpCreatePreMulSum) or a wide sum
-// (dcclRedOpCreateWideSum, fp16 / bf16 accumulated in fp32; no scalar); handle = ncclNumOps + its slot.
+// A user op of a communicator: a pre-multiplied sum (ncclRedOpCreatePreMulSum), a wide sum (dcclRedOpCreateWideSum,
+// fp16 / bf16 accumulated in fp32; no scalar) or a scaled wide sum (dcclRedOpCreateWideScaledSum: the wide sum's
+// accumulator times one fp32 scalar, which bits / dev_ptr hold); handle = ncclNumOps + its slot.
 constexpr int kMaxUserOps = 16;
-enum UserOpKind : int { kPremulSum = 0, kWideSum = 1 };
+enum UserOpKind : int { kPremulSum = 0, kWideSum = 1, kWideScaledSum = 2 };
 struct UserOp {
     bool live = false;
     int kind = kPremulSum;
@@ -102,7 +103,9 @@ struct UserOp {
     const void* dev_ptr = nullptr;  // ncclScalarDevice: read by each collective's kernels when they run
 };
 // What a collective hands down for such an op: dccl_local_scale's (scalar, residence); scalar nullptr = none.
-// `wide`: a wide sum (never together with a scalar): the chain launch becomes dccl_local_reduce_chain_wide.
+// `wide`: a wide sum: the chain launch becomes dccl_local_reduce_chain_wide.  `wide` with a scalar: a scaled wide
+// sum; the scalar is then ONE fp32 that multiplies the finished accumulator (dccl_local_reduce_chain_wide_scaled,
+// dccl_local_convert_scaled) and never reaches the 16-bit pre-multiplication: every reader tests `wide` first.
 struct PremulArg {
     const void* scalar = nullptr;
     int residence = 0;

@@ -86,7 +86,8 @@ ncclResult_t copy_bytes(void* dst, const void* src, size_t bytes, bool device, h
 }
 
 // A pre-multiplied-sum handle that is live on `c` becomes (ncclSum, its scalar), a wide-sum handle (ncclSum, the
-// wide flag); every other op value keeps today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything
+// wide flag), a scaled-wide-sum handle (ncclSum, the wide flag and its fp32 scalar); every other op value keeps
+// today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything
 // else -> ncclInvalidArgument).
 ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, PremulArg* pm) {
     const int slot = *op - int(dccl::ncclNumOps);
@@ -94,19 +95,19 @@ ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, PremulArg* pm) {
     const UserOp& u = c->user_ops[slot];
     if (u.dtype != dtype) return dccl::ncclInvalidArgument;
     *op = dccl::ncclSum;
-    if (u.kind == kWideSum) {  // (ncclSum, wide flag): no scalar
-        pm->wide = true;
-        return dccl::ncclSuccess;
-    }
+    pm->wide = u.kind != kPremulSum;
+    if (u.kind == kWideSum) return dccl::ncclSuccess;  // (ncclSum, wide flag): no scalar
     pm->scalar = u.dev_ptr != nullptr ? u.dev_ptr : static_cast<const void*>(&u.bits);
     pm->residence = u.dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate;
     return dccl::ncclSuccess;
 }
 
 // The collectives' first step outside the direct paths: dst = src, or dst = src * scalar for a pre-multiplied sum
-// (in place when src == dst), after which the algorithm runs with ncclSum.
+// (in place when src == dst), after which the algorithm runs with ncclSum.  A wide op never comes here (wide_staged
+// takes it first): its scalar is an fp32 that multiplies the finished sum, not an element of `dtype`.
 ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, const PremulArg& pm, bool device,
                          hipStream_t st) {
+    if (pm.wide) return dccl::ncclInternalError;
     if (pm.scalar == nullptr) return copy_bytes(dst, src, count * size_of_dtype(dtype), device, st);
     return static_cast<ncclResult_t>(dccl_local_scale(src, dst, dtype, count, pm.scalar, pm.residence, st));
 }
@@ -463,7 +464,7 @@ struct Call {
     int dtype = 0;
     int user_op = 0;           // the op value as passed (a pre-multiplied-sum handle included): the run key
     int op = 0;                // resolved: a built-in op
-    PremulArg pm;              // resolved: the pre-multiplied sum's scalar, or none
+    PremulArg pm;              // resolved: the pre-multiplied sum's scalar, the wide flag (with its scalar), or none
     uint64_t bits = 0;         // a queued host-immediate scalar's own copy
     int root = 0;
     bool dev = false;
@@ -532,7 +533,7 @@ ncclResult_t ar_run(const Call& c, hipStream_t stream) {
     if (W > 1 && !dev && host_direct_selected(comm, total / W))
         return direct_all_reduce_host(comm, sendbuff, recvbuff, count, datatype, op);
     if (pm.wide) return wide_staged(c, stream);
-    if (W > 1 && algo != Algorithm::kRabenseifner && pm.scalar == nullptr && grouped_selected(comm, dev))
+    if (W > 1 && algo != Algorithm::kRabenseifner && !pm.wide && pm.scalar == nullptr && grouped_selected(comm, dev))
         return all_reduce_grouped(comm, sendbuff, recvbuff, count, datatype, op, stream);
     rc = stage_input(recvbuff, sendbuff, count, datatype, pm, dev, stream);  // dccl.cpp:393-408
     if (rc != ncclSuccess) return rc;
@@ -583,7 +584,7 @@ ncclResult_t rs_run(const Call& c, hipStream_t stream) {
         return direct_reduce_scatter_host(comm, sendbuff, recvbuff, recvcount, datatype, op);
     if (pm.wide) return wide_staged(c, stream);
     // slot r, reduced straight from sendbuff: no work copy (a pre-multiplied sum scales into the work copy: the ring)
-    if (W > 1 && pm.scalar == nullptr && grouped_selected(comm, dev))
+    if (W > 1 && !pm.wide && pm.scalar == nullptr && grouped_selected(comm, dev))
         return reduce_scatter_grouped(comm, sendbuff, recvbuff, recvcount * W, datatype, op, stream, 0);
     if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
     void* work = dev ? comm->dev_work : comm->host_work;
@@ -770,13 +771,19 @@ ncclResult_t run_plain(const Call& c) {
 // fp32 staging buffer, run the ncclFloat32 / ncclSum collective these settings select on it (ring, Rabenseifner,
 // p2p, RCCL ring or grouped), and round its result once into recvbuff (ncclReduce: on the root only).  A
 // reduce-scatter's fp32 result lies behind the widened input.  The staging buffer is not dev_work: rs_run and
-// reduce_run grow that one underneath.  W == 1: the input's bytes.
+// reduce_run grow that one underneath.  W == 1: the input's bytes.  A scaled wide sum (c.pm.scalar, one fp32)
+// takes the same route with dccl_local_convert_scaled as the narrowing pass, which multiplies as it rounds; the
+// fp32 collective in the middle never sees the scalar.  Its W == 1 is that pass from 16 bits to 16 bits.
 ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
     dcclComm* comm = c.comm;
     const uint32_t W = comm->world;
     const bool rs = c.api == group::kReduceScatter;
     const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
     const bool has_out = c.api != group::kReduce || comm->rank == uint32_t(c.root);
+    const PremulArg& pm = c.pm;
+    if (W == 1 && pm.scalar != nullptr)
+        return static_cast<ncclResult_t>(
+            dccl_local_convert_scaled(c.send, c.dtype, c.recv, c.dtype, out_count, pm.scalar, pm.residence, stream));
     if (W == 1) return copy_bytes(c.recv, c.send, out_count * size_of_dtype(c.dtype), true, stream);
     ncclResult_t rc = ensure_wide(comm, (in_count + (rs ? out_count : 0)) * sizeof(float));
     if (rc != ncclSuccess) return rc;
@@ -792,6 +799,9 @@ ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
     f.stream = stream;
     rc = run_plain(f);
     if (rc != ncclSuccess || !has_out) return rc;
+    if (pm.scalar != nullptr)
+        return static_cast<ncclResult_t>(dccl_local_convert_scaled(f.recv, ncclFloat32, c.recv, c.dtype, out_count,
+                                                                   pm.scalar, pm.residence, stream));
     return static_cast<ncclResult_t>(dccl_local_convert(f.recv, ncclFloat32, c.recv, c.dtype, out_count, stream));
 }
 
@@ -818,8 +828,9 @@ size_t coalesce_max_bytes() {
     return group::kDefaultMaxBytes;
 }
 
-// Inside a group: a validated call joins the queue.  The scalar of a host-immediate pre-multiplied sum is kept in
-// the entry itself (run_queue points the entry's PremulArg at it), so nothing refers to the op's slot later.
+// Inside a group: a validated call joins the queue.  The scalar of a host-immediate pre-multiplied sum (or scaled
+// wide sum: one fp32 inside the same 8 bytes) is kept in the entry itself (run_queue points the entry's PremulArg
+// at it), so nothing refers to the op's slot later.
 ncclResult_t enqueue(Call c, hipStream_t stream) {
     c.stream = stream;
     if (c.pm.scalar != nullptr && c.pm.residence == ncclScalarHostImmediate) {
@@ -1028,6 +1039,27 @@ ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, nc
     return ncclInvalidUsage;  // kMaxUserOps live ops already
 }
 
+ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, ncclDataType_t datatype,
+                                          ncclScalarResidence_t residence, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    if (op == nullptr || scalar == nullptr) return ncclInvalidArgument;
+    if (residence != ncclScalarDevice && residence != ncclScalarHostImmediate) return ncclInvalidArgument;
+    if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
+    for (int slot = 0; slot < kMaxUserOps; ++slot) {
+        UserOp& u = comm->user_ops[slot];
+        if (u.live) continue;
+        u = UserOp{};
+        u.live = true;
+        u.kind = kWideScaledSum;
+        u.dtype = datatype;
+        if (residence == ncclScalarDevice) u.dev_ptr = scalar;
+        else std::memcpy(&u.bits, scalar, sizeof(float));  // always one fp32, whatever the datatype
+        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
+        return ncclSuccess;
+    }
+    return ncclInvalidUsage;  // kMaxUserOps live ops already
+}
+
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
     validate_comm(comm, __func__);
     const int slot = int(op) - int(ncclNumOps);
@@ -1198,6 +1230,18 @@ extern "C" int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm) {
         dccl::ncclRedOp_t h = dccl::ncclSum;
         const ncclResult_t rc = dccl::dcclRedOpCreateWideSum(
             op != nullptr ? &h : nullptr, static_cast<dccl::ncclDataType_t>(dtype), static_cast<dccl::ncclComm_t>(comm));
+        if (rc == dccl::ncclSuccess) *op = int(h);
+        return rc;
+    });
+}
+
+extern "C" int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, int dtype, int residence, void* comm) {
+    if (residence != 0 && residence != 1) return DCCL_INVALID_ARGUMENT;  // before the cast to the two-value enum
+    return guarded([&] {
+        dccl::ncclRedOp_t h = dccl::ncclSum;
+        const ncclResult_t rc = dccl::dcclRedOpCreateWideScaledSum(
+            op != nullptr ? &h : nullptr, scalar, static_cast<dccl::ncclDataType_t>(dtype),
+            static_cast<dccl::ncclScalarResidence_t>(residence), static_cast<dccl::ncclComm_t>(comm));
         if (rc == dccl::ncclSuccess) *op = int(h);
         return rc;
     });

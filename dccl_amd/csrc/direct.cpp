@@ -629,14 +629,20 @@ ncclResult_t chain(const Peers& P, uint32_t W, uint32_t first, size_t off, const
     if (fault_injected("direct_combine", rank)) return dccl::ncclUnhandledCudaError;
     const void* sends[kDirectMaxWorld];
     for (uint32_t j = 0; j + 1 < W; ++j) sends[j] = P.in[(first + j) % W] + off;
+    // `pm` wide: a wide sum (fp16 / bf16, op is ncclSum), the same chain accumulated in fp32 and rounded once; with
+    // a scalar (one fp32) the accumulator is multiplied by it before that rounding.  Tested before the scalar alone:
+    // a wide op's scalar must never reach the 16-bit pre-multiplication.
+    if (pm != nullptr && pm->wide) {
+        if (pm->scalar != nullptr)
+            return static_cast<ncclResult_t>(dccl_local_reduce_chain_wide_scaled(
+                sends, int(W - 1), own, dst, dtype, elems, pm->scalar, pm->residence, static_cast<void*>(st)));
+        return static_cast<ncclResult_t>(
+            dccl_local_reduce_chain_wide(sends, int(W - 1), own, dst, dtype, elems, static_cast<void*>(st)));
+    }
     // `pm` with a scalar: a pre-multiplied sum (op is ncclSum), the same chain with every operand scaled as it is read
     if (pm != nullptr && pm->scalar != nullptr)
         return static_cast<ncclResult_t>(dccl_local_reduce_chain_premul(
             sends, int(W - 1), own, dst, dtype, elems, pm->scalar, pm->residence, static_cast<void*>(st)));
-    // `pm` wide: a wide sum (fp16 / bf16, op is ncclSum), the same chain accumulated in fp32 and rounded once
-    if (pm != nullptr && pm->wide)
-        return static_cast<ncclResult_t>(
-            dccl_local_reduce_chain_wide(sends, int(W - 1), own, dst, dtype, elems, static_cast<void*>(st)));
     return static_cast<ncclResult_t>(
         dccl_local_reduce_chain(sends, int(W - 1), own, dst, dtype, elems, op, static_cast<void*>(st)));
 }

@@ -50,7 +50,8 @@ bool direct_selected(const dccl::dcclComm* c);
 
 // `pm` (here and in direct_reduce_scatter / direct_reduce): a pre-multiplied sum (comm.hpp PremulArg; op is
 // ncclSum then): the chain launch multiplies every contribution by the scalar as it reads it.  With pm->wide (a
-// wide sum, fp16 / bf16) the chain launch accumulates in fp32 and rounds once; the bytes moved are unchanged.
+// wide sum, fp16 / bf16) the chain launch accumulates in fp32 and rounds once; the bytes moved are unchanged.  With
+// pm->wide and a scalar (a scaled wide sum) the scalar is one fp32 that multiplies the accumulator before the rounding.
 ncclResult_t direct_all_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
                                hipStream_t st, const PremulArg* pm = nullptr);
 

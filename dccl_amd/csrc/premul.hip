@@ -13,9 +13,8 @@
 //   * fp16 / bf16: widen to fp32, multiply, ROUND BACK to 16 bits; the Sum widens again.  (fp16 needs the
 //     contraction switch as well: see PreMul<f16_bits>.)
 //   * integers wrap (8-bit types truncate).
-// The scalar travels as a kernel argument {bits, dev_ptr}: with dev_ptr set every wave loads it from device
-// memory when it runs (stream-ordered, so a captured graph replays with the value of the moment); otherwise
-// `bits` holds the value the host read at the call.  Every store is an ordinary vector store.
+// The scalar travels as scalar_arg.hpp's ScalarArg (read by the host at the call, or by every wave from device
+// memory when it runs).  Every store is an ordinary vector store.
 //
 // The chain kernels are reduce_kernels.hpp's chain bodies (the plain chain's tile loop, loads, ring order and edge
 // elements) with the PremulChain policy below; their placement rule and launch are chain_forms.hpp's.  The scale
@@ -24,26 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 
 #include "chain_forms.hpp"
 #include "dccl/dccl_reduce.h"
+#include "scalar_arg.hpp"
 
 namespace dccl_amd {
 namespace {
-
-struct ScalarArg {
-    uint64_t bits;        // the scalar's bytes (host-immediate residence)
-    const void* dev_ptr;  // non-null: read the scalar here when the kernel runs (device residence)
-};
-
-template <typename T>
-__device__ __forceinline__ T load_scalar(const ScalarArg& a) {
-    if (a.dev_ptr != nullptr) return ld_elem<T, false>(static_cast<const unsigned char*>(a.dev_ptr), 0);
-    T s;
-    __builtin_memcpy(&s, &a.bits, sizeof(T));
-    return s;
-}
 
 // x * s with Prod's element semantics; 16-bit floats come back rounded to 16 bits.
 template <typename T> struct PreMul {
@@ -182,16 +168,6 @@ struct PremulChainFn {
     }
 };
 
-bool scalar_ok(const void* scalar, int residence) { return scalar != nullptr && (residence == 0 || residence == 1); }
-
-// residence 0: the device address itself; 1: the host value, read now
-ScalarArg make_scalar(const void* scalar, int residence, int dtype) {
-    ScalarArg sa{0, nullptr};
-    if (residence == 0) sa.dev_ptr = scalar;
-    else std::memcpy(&sa.bits, scalar, size_of_dtype(dtype));
-    return sa;
-}
-
 }  // namespace
 }  // namespace dccl_amd
 
@@ -204,7 +180,7 @@ extern "C" int dccl_local_scale(const void* src, void* dst, int dtype, size_t co
     if (count == 0) return DCCL_SUCCESS;
     if (src == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
     if (partial_overlap(src, dst, count * size_of_dtype(dtype))) return DCCL_INVALID_ARGUMENT;
-    return dispatch<ScaleFn>(dtype, kSum, src, dst, count, make_scalar(scalar, residence, dtype),
+    return dispatch<ScaleFn>(dtype, kSum, src, dst, count, make_scalar(scalar, residence, size_of_dtype(dtype)),
                              static_cast<hipStream_t>(stream));
 }
 
@@ -215,6 +191,7 @@ extern "C" int dccl_local_reduce_chain_premul(const void* const* sends, int nsen
     if (!scalar_ok(scalar, residence)) return DCCL_INVALID_ARGUMENT;  // the same code as a bad nsend, before count == 0
     const int rc = check_chain_args(sends, nsend, own, dst, count * size_of_dtype(dtype));
     if (rc != DCCL_SUCCESS || count == 0) return rc;
-    return dispatch<PremulChainFn>(dtype, kSum, sends, nsend, own, dst, count, make_scalar(scalar, residence, dtype),
+    return dispatch<PremulChainFn>(dtype, kSum, sends, nsend, own, dst, count,
+                                   make_scalar(scalar, residence, size_of_dtype(dtype)),
                                    static_cast<hipStream_t>(stream));
 }

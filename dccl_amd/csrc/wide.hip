@@ -1,17 +1,21 @@
 // dccl_amd/csrc/wide.hip — wide sum (dcclRedOpCreateWideSum): fp16 / bf16 contributions accumulated in fp32 and
-// rounded to 16 bits once.
+// rounded to 16 bits once, and its scaled form (dcclRedOpCreateWideScaledSum, §7.8): the finished
+// fp32 accumulator times one fp32 scalar s, then the one rounding.
 //
-//   dccl_local_reduce_chain_wide   acc = widen(sends[0][i]); acc = widen(sends[j][i]) + acc, j = 1..k-1;
-//                                  acc = widen(own[i]) + acc;  dst[i] = round16(acc)
-//   dccl_local_convert             dst[i] = widen(src[i]) (fp16 / bf16 -> fp32, exact) or round16(src[i])
-//                                  (fp32 -> fp16 / bf16, nearest-even)
+//   dccl_local_reduce_chain_wide          acc = widen(sends[0][i]); acc = widen(sends[j][i]) + acc, j = 1..k-1;
+//                                         acc = widen(own[i]) + acc;  dst[i] = round16(acc)
+//   dccl_local_reduce_chain_wide_scaled   the same acc;  dst[i] = round16(acc * s)
+//   dccl_local_convert                    dst[i] = widen(src[i]) (fp16 / bf16 -> fp32, exact) or round16(src[i])
+//                                         (fp32 -> fp16 / bf16, nearest-even)
+//   dccl_local_convert_scaled             dst[i] = round16(as_fp32(src[i]) * s), src fp32 or dst's own 16-bit type
 //
 // widen and round16 are combine.hpp's f16_to_f32 / bf16_to_f32 / f32_to_f16 / f32_to_bf16, the conversions the Sum
 // combine itself applies, and every add is one IEEE fp32 add in dccl_local_reduce_chain's order (sends[0] first,
 // own last).  The chain therefore gives the bits of "widen every operand, run the fp32 Sum chain, round once";
 // with one source it gives the plain 16-bit chain's bits (one add, one rounding).  It reads and writes what the
-// plain chain does: 16-bit operands in, 16 bits out.  There is no pre-multiplied form.  Every store is an
-// ordinary vector store.
+// plain chain does: 16-bit operands in, 16 bits out.  The scaled form multiplies AFTER the sum (one IEEE fp32
+// multiply per element, never fused with an add; a wide sum of pre-multiplied contributions does not exist); its
+// scalar travels as scalar_arg.hpp's ScalarArg.  Every store is an ordinary vector store.
 //
 // The chain kernels are reduce_kernels.hpp's chain bodies (the plain chain's tile loop, loads, ring order and edge
 // elements) with the WideChain policy below, eight fp32 accumulators per lane; their placement rule and launch are
@@ -21,9 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "chain_forms.hpp"
 #include "dccl/dccl_reduce.h"
+#include "scalar_arg.hpp"
 
 namespace dccl_amd {
 namespace {
@@ -81,6 +87,57 @@ struct WideChain {
     __device__ __forceinline__ T finish(float acc) const { return Wide<T>::narrow(acc); }
 };
 
+// acc * s on its way to the 16-bit rounding of ONE element (edge elements, element-wise kernels): one IEEE fp32
+// multiply, rounded to fp32 (no contraction: nothing may fuse it with an add of the chain).  For fp16 the product
+// then passes an identity lane move (every lane reads itself).  Without it hipcc selects v_fma_mixlo_f16 /
+// v_fma_mixhi_f16 for "fp32 multiply, convert to fp16", one instruction for both steps, wherever a conversion is not
+// half of a packed pair.  On gfx950 its results are not those of the fp32 rounding followed by the fp16 rounding
+// that the contract states: they differ where the exact product rounds differently in one step than in two, about
+// 1 % of elements with s = 0.3.  No pragma or flag reaches that selection; the move keeps
+// v_mul_f32 and v_cvt_f16_f32 two instructions.  bf16 has no such instruction.
+template <typename T>
+__device__ __forceinline__ float scale1(float acc, float s) {
+#pragma clang fp contract(off)
+    const float p = acc * s;
+    if constexpr (std::is_same_v<T, f16_bits>)  // quad_perm [0, 1, 2, 3], every row and bank: the identity
+        return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, p), 0xE4, 0xF, 0xF, true));
+    else return p;
+}
+// Eight products, rounded: bf16 lane by lane; fp16 as four explicit pairs, a 2-vector multiply and a 2-vector
+// conversion (v_pk_mul_f32, v_cvt_pk_f16_f32), which the compiler keeps two instructions: no lane moves in the
+// vector loops, and no lane left for the fused instruction above.
+template <typename T>
+__device__ __forceinline__ u32x4 narrow_scaled16(const F32x8& acc, float s) {
+    if constexpr (std::is_same_v<T, f16_bits>) {
+#pragma clang fp contract(off)
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        struct { f16x2 h[kLanes16 / 2]; } p;
+#pragma unroll
+        for (int i = 0; i < kLanes16 / 2; ++i)
+            p.h[i] = __builtin_convertvector(f32x2{acc.f[2 * i], acc.f[2 * i + 1]} * s, f16x2);
+        return __builtin_bit_cast(u32x4, p);
+    } else {
+        Pack<T> p;
+#pragma unroll
+        for (int i = 0; i < kLanes16; ++i) p.e[i] = Wide<T>::narrow(scale1<T>(acc.f[i], s));
+        return __builtin_bit_cast(u32x4, p);
+    }
+}
+
+// WideChain carrying the fp32 scalar: the finished accumulators are multiplied by s, then rounded once.
+template <typename T>
+struct WideScaledChain {
+    using Elem = T;
+    float s;
+    __device__ __forceinline__ F32x8 first16(u32x4 v) const { return widen16<T>(v); }
+    __device__ __forceinline__ F32x8 fold16(u32x4 v, F32x8 acc) const { return add16<T>(v, acc); }
+    __device__ __forceinline__ u32x4 finish16(const F32x8& acc) const { return narrow_scaled16<T>(acc, s); }
+    __device__ __forceinline__ float first(T x) const { return Wide<T>::widen(x); }
+    __device__ __forceinline__ float fold(T x, float acc) const { return Wide<T>::widen(x) + acc; }
+    __device__ __forceinline__ T finish(float acc) const { return Wide<T>::narrow(scale1<T>(acc, s)); }
+};
+
 // ---- chain: reduce_chain_vec_kernel's roles and order, one fp32 accumulator per element ----
 template <typename T, int K, typename C>
 __global__ __launch_bounds__(C::BLOCK) void wide_chain_vec_kernel(SendList sends, const unsigned char* own,
@@ -94,6 +151,22 @@ template <typename T, bool ALIGNED>
 __global__ __launch_bounds__(kBlock) void wide_chain_elem_kernel(SendList sends, int nsend, const unsigned char* own,
                                                                  unsigned char* dst, size_t count) {
     chain_elem_body<WideChain<T>, ALIGNED>(sends, nsend, own, dst, count, WideChain<T>{});
+}
+
+template <typename T, int K, typename C>
+__global__ __launch_bounds__(C::BLOCK) void wide_scaled_chain_vec_kernel(SendList sends, const unsigned char* own,
+                                                                         unsigned char* dst, size_t head, size_t nvec,
+                                                                         size_t tail, ScalarArg sa) {
+    chain_vec_body<WideScaledChain<T>, K, C>(sends, own, dst, head, nvec, tail,
+                                             WideScaledChain<T>{load_scalar<float>(sa)});
+}
+
+template <typename T, bool ALIGNED>
+__global__ __launch_bounds__(kBlock) void wide_scaled_chain_elem_kernel(SendList sends, int nsend,
+                                                                        const unsigned char* own, unsigned char* dst,
+                                                                        size_t count, ScalarArg sa) {
+    chain_elem_body<WideScaledChain<T>, ALIGNED>(sends, nsend, own, dst, count,
+                                                 WideScaledChain<T>{load_scalar<float>(sa)});
 }
 
 // ---- convert: `half` is the 16-bit side, `full` the fp32 side; WIDEN: half -> full, else full -> half ----
@@ -134,12 +207,63 @@ __global__ __launch_bounds__(kBlock) void convert_elem_kernel(const unsigned cha
     }
 }
 
+// ---- scaled convert: dst (T) = round16(as_fp32(src) * s); S is float (the staged route's narrowing pass) or T
+// (its W = 1 case: 16 B against 16 B, src may be dst) ----
+template <typename T, typename S, bool ALIGNED>
+__device__ __forceinline__ float ld_as_f32(const unsigned char* src, size_t i) {
+    if constexpr (sizeof(S) == sizeof(float)) return ld_elem<float, ALIGNED>(src, i);
+    else return Wide<T>::widen(ld_elem<T, ALIGNED>(src, i));
+}
+
+template <typename T, typename S>
+__global__ __launch_bounds__(64) void convert_scaled_vec_kernel(const unsigned char* src, unsigned char* dst,
+                                                                size_t head, size_t nvec, size_t tail, ScalarArg sa) {
+    const float s = load_scalar<float>(sa);
+    const u32x4* vs = reinterpret_cast<const u32x4*>(src + head * sizeof(S));
+    u32x4* vd = reinterpret_cast<u32x4*>(dst + head * sizeof(T));
+    const size_t ntiles = (nvec + 63) / 64;
+    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const size_t i = t * 64 + threadIdx.x;
+        if (i >= nvec) continue;
+        F32x8 w;
+        if constexpr (sizeof(S) == sizeof(float)) {
+            const U32x4x2 v{{ld16<true>(vs + 2 * i), ld16<true>(vs + 2 * i + 1)}};
+            w = __builtin_bit_cast(F32x8, v);
+        } else {
+            w = widen16<T>(ld16<true>(vs + i));
+        }
+        __builtin_nontemporal_store(narrow_scaled16<T>(w, s), vd + i);
+    }
+    if (blockIdx.x == 0)
+        for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
+            const size_t i = edge_index<T>(j, head, nvec);
+            st_elem<T, true>(dst, i, Wide<T>::narrow(scale1<T>(ld_as_f32<T, S, true>(src, i), s)));
+        }
+}
+
+template <typename T, typename S, bool ALIGNED>
+__global__ __launch_bounds__(kBlock) void convert_scaled_elem_kernel(const unsigned char* src, unsigned char* dst,
+                                                                     size_t count, ScalarArg sa) {
+    const float s = load_scalar<float>(sa);
+    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < count; i += size_t(gridDim.x) * kBlock)
+        st_elem<T, ALIGNED>(dst, i, Wide<T>::narrow(scale1<T>(ld_as_f32<T, S, ALIGNED>(src, i), s)));
+}
+
 // ---- launches ----
 struct WideChainKernels {  // chain_forms.hpp launch_chain_form
     template <typename T, int K>
     static const void* vec() { return reinterpret_cast<const void*>(&wide_chain_vec_kernel<T, K, DefaultCfg>); }
     template <typename T, bool ALIGNED>
     static const void* elem() { return reinterpret_cast<const void*>(&wide_chain_elem_kernel<T, ALIGNED>); }
+};
+
+struct WideScaledChainKernels {
+    template <typename T, int K>
+    static const void* vec() {
+        return reinterpret_cast<const void*>(&wide_scaled_chain_vec_kernel<T, K, DefaultCfg>);
+    }
+    template <typename T, bool ALIGNED>
+    static const void* elem() { return reinterpret_cast<const void*>(&wide_scaled_chain_elem_kernel<T, ALIGNED>); }
 };
 
 template <typename T, bool WIDEN>
@@ -162,6 +286,28 @@ int convert_typed(const void* src, void* dst, size_t count, hipStream_t stream) 
     Split sp{head, nvec, count - head - nvec * kLanes16};
     void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&convert_vec_kernel<T, WIDEN>), grid_for(sp, 64), args, stream, 64);
+}
+
+// convert_typed's placement rule with dst as the 16-bit side: head elements bring dst to a 16-B boundary, and src
+// (fp32, or 16 bits wide like dst) must be on one there too; any other placement takes the element-wise kernel.
+template <typename T, typename S>
+int convert_scaled_typed(const void* src, void* dst, size_t count, ScalarArg sa, hipStream_t stream) {
+    auto s = static_cast<const unsigned char*>(src);
+    auto d = static_cast<unsigned char*>(dst);
+    const uintptr_t as = reinterpret_cast<uintptr_t>(src), ad = reinterpret_cast<uintptr_t>(dst);
+    const bool elem_ok = ad % sizeof(T) == 0 && as % sizeof(S) == 0;
+    size_t head = elem_ok ? ((16 - (ad & 15)) & 15) / sizeof(T) : 0;
+    if (!elem_ok || ((as + head * sizeof(S)) & 15)) {
+        void* args[] = {&s, &d, &count, &sa};
+        const void* fn = elem_ok ? reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, true>)
+                                 : reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, false>);
+        return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
+    }
+    if (head > count) head = count;
+    const size_t nvec = (count - head) / kLanes16;
+    Split sp{head, nvec, count - head - nvec * kLanes16};
+    void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail, &sa};
+    return launch(reinterpret_cast<const void*>(&convert_scaled_vec_kernel<T, S>), grid_for(sp, 64), args, stream, 64);
 }
 
 bool is_16bit_float(int dtype) { return dtype == kFloat16 || dtype == kBfloat16; }
@@ -202,4 +348,39 @@ extern "C" int dccl_local_convert(const void* src, int src_dtype, void* dst, int
                                      : convert_typed<bf16_bits, true>(src, dst, count, st);
     return dst_dtype == kFloat16 ? convert_typed<f16_bits, false>(src, dst, count, st)
                                  : convert_typed<bf16_bits, false>(src, dst, count, st);
+}
+
+extern "C" int dccl_local_reduce_chain_wide_scaled(const void* const* sends, int nsend, const void* own, void* dst,
+                                                   int dtype, size_t count, const void* scalar, int residence,
+                                                   void* stream) {
+    if (!is_16bit_float(dtype)) return DCCL_INVALID_ARGUMENT;
+    if (!scalar_ok(scalar, residence)) return DCCL_INVALID_ARGUMENT;  // where dccl_local_reduce_chain_premul has it
+    const int rc = check_chain_args(sends, nsend, own, dst, count * size_of_dtype(dtype));
+    if (rc != DCCL_SUCCESS || count == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ScalarArg sa = make_scalar(scalar, residence, sizeof(float));
+    return dtype == kFloat16
+               ? launch_chain_form<WideScaledChainKernels, f16_bits>(sends, nsend, own, dst, count, st, sa)
+               : launch_chain_form<WideScaledChainKernels, bf16_bits>(sends, nsend, own, dst, count, st, sa);
+}
+
+extern "C" int dccl_local_convert_scaled(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count,
+                                         const void* scalar, int residence, void* stream) {
+    const bool from32 = src_dtype == kFloat32 && is_16bit_float(dst_dtype);
+    const bool same16 = src_dtype == dst_dtype && is_16bit_float(dst_dtype);
+    if (!from32 && !same16) return DCCL_INVALID_ARGUMENT;
+    if (!scalar_ok(scalar, residence)) return DCCL_INVALID_ARGUMENT;
+    if (count == 0) return DCCL_SUCCESS;
+    if (src == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
+    // fp32 source: no shared byte (dccl_local_convert's rule); 16-bit source: src == dst or no shared byte
+    if (from32 ? ranges_intersect(src, count * sizeof(float), dst, count * size_of_dtype(dst_dtype))
+               : partial_overlap(src, dst, count * size_of_dtype(dst_dtype)))
+        return DCCL_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ScalarArg sa = make_scalar(scalar, residence, sizeof(float));
+    if (from32)
+        return dst_dtype == kFloat16 ? convert_scaled_typed<f16_bits, float>(src, dst, count, sa, st)
+                                     : convert_scaled_typed<bf16_bits, float>(src, dst, count, sa, st);
+    return dst_dtype == kFloat16 ? convert_scaled_typed<f16_bits, f16_bits>(src, dst, count, sa, st)
+                                 : convert_scaled_typed<bf16_bits, bf16_bits>(src, dst, count, sa, st);
 }

@@ -115,8 +115,24 @@ ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm);
  *  unchanged (it rounds after every combine step).  The direct collectives move the 16-bit bytes they move for
  *  ncclSum; every other path stages through an fp32 buffer of the communicator.  NULL `op` or
  *  another datatype: ncclInvalidArgument; a 17th live op: ncclInvalidUsage; host buffers: ncclInvalidUsage.
- *  A wide sum cannot be combined with a pre-multiplied scalar. */
+ *  A wide sum cannot be combined with a pre-multiplied scalar (one applied to every contribution); for a scalar
+ *  applied to the finished sum see dcclRedOpCreateWideScaledSum. */
 ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, ncclComm_t comm);
+
+/** Scaled wide sum: the wide sum above whose finished fp32 accumulator is multiplied by `scalar` before the one
+ *  rounding: result = round16(fp32_mul(fp32 sum of the widened contributions, s)), e.g. s = 1.0f / W for the mean
+ *  of 16-bit gradients.  `scalar` is ALWAYS one fp32, whatever `datatype` (ncclFloat16 or ncclBfloat16 only), so
+ *  1/3 is the fp32 1/3.  ncclScalarDevice: a device float, read by each collective's kernels when they run;
+ *  ncclScalarHostImmediate: host memory, read before this call returns.  Every rank must pass the same value.
+ *  The results are the bits of running the ncclFloat32 / ncclSum collective of the wide sum, multiplying its result
+ *  by s in fp32 and rounding to nearest-even; with s = 1.0f they are the wide sum's.  W = 1 gives
+ *  round16(widen(x) * s), not a byte copy.  The handle comes from the same table (ncclNumOps + slot, 16 live ops
+ *  per communicator together; ncclRedOpDestroy releases it).  The direct collectives fuse the multiply into their
+ *  chain launch, every other path into the narrowing pass it already runs: no extra pass over memory.  NULL `op`
+ *  or `scalar`, a bad residence or another datatype: ncclInvalidArgument; a 17th live op: ncclInvalidUsage; host
+ *  buffers: ncclInvalidUsage; another datatype at the collective: ncclInvalidArgument. */
+ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, ncclDataType_t datatype,
+                                          ncclScalarResidence_t residence, ncclComm_t comm);
 
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);

@@ -104,7 +104,13 @@
  *                         IPC) fuse it into their one chain launch and move the 16-bit bytes; ring,
  *                         Rabenseifner, plugged-in p2p and RCCL paths widen into an fp32 buffer of the
  *                         communicator, run the fp32 Sum collective there and narrow into recv.  There is no
- *                         combination with a pre-multiplied scalar.
+ *                         combination with a pre-multiplied scalar (one applied to every contribution).
+ *   dccl_red_op_create_wide_scaled_sum  dcclRedOpCreateWideScaledSum: the wide sum whose finished fp32 accumulator
+ *                         is multiplied by `scalar` (ONE fp32 whatever the dtype; `residence` as above) before the
+ *                         one rounding, e.g. 1.0f / W for a mean.  Same table, handles and rules as the wide sum;
+ *                         the same scalar on every rank.  Create: NULL op or scalar, a residence other than 0 / 1
+ *                         or a dtype other than 6 / 9 -> 4; a 17th live op -> 5.  The direct collectives fuse the
+ *                         multiply into their chain launch, the staged paths into their narrowing pass.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -136,6 +142,7 @@ int dccl_broadcast(const void* send, void* recv, size_t count, int dtype, int ro
 int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
 int dccl_red_op_destroy(int op, void* comm);
 int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm);
+int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
 int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);

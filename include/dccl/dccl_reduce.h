@@ -116,7 +116,8 @@ int dccl_local_reduce_chain_premul(const void* const* sends, int nsend, const vo
  *                                  once.  With nsend == 1 that equals dccl_local_reduce_chain with op Sum.
  *   dccl_local_convert             dst[i] = widen(src[i]) for (src_dtype, dst_dtype) = (6, 7) or (9, 7),
  *                                  dst[i] = round16(src[i]) for (7, 6) or (7, 9); any other pair 4.
- * NaN payloads are unpinned, as everywhere.  There is no pre-multiplied form of the wide sum.
+ * NaN payloads are unpinned, as everywhere.  The wide sum has no pre-multiplied form (a scalar applied to every
+ * contribution); its scaled form, one multiply of the finished sum, follows below.
  * Validation, in this order: dtype not 6 / 9 (convert: an unsupported pair) 4, unknown dtypes included; nsend
  * outside 1..8 or NULL sends 4; count == 0 succeeds; NULL operand 4; chain: an operand partially overlapping dst
  * 4 (own == dst and a source == dst are allowed); convert: src and dst sharing ANY byte 4 (their element sizes
@@ -129,6 +130,32 @@ int dccl_local_reduce_chain_premul(const void* const* sends, int nsend, const vo
 int dccl_local_reduce_chain_wide(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
                                  size_t count, void* stream);
 int dccl_local_convert(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count, void* stream);
+
+/*
+ * Scaled wide sum (the device half of dcclRedOpCreateWideScaledSum, include/dccl/dccl.hpp): the wide sum's finished
+ * fp32 accumulator is multiplied by one fp32 scalar s and rounded to 16 bits once, e.g. s = 1/W for a mean.
+ *   dccl_local_reduce_chain_wide_scaled   dccl_local_reduce_chain_wide's accumulator, roles, limits and aliasing
+ *                                         rule; dst[i] = round16(acc * s): one IEEE fp32 multiply (never fused
+ *                                         with an add), then the one nearest-even rounding.  With s = 1.0f the
+ *                                         bits of dccl_local_reduce_chain_wide.
+ *   dccl_local_convert_scaled             dst[i] = round16(as_fp32(src[i]) * s) for (src_dtype, dst_dtype) =
+ *                                         (7, 6), (7, 9), (6, 6) or (9, 9); any other pair 4.  It is the narrowing
+ *                                         pass of the staged collectives; the 16 -> 16 pairs are their W = 1 case.
+ * `scalar` points to ONE fp32 whatever the operands' dtype; `residence` as for the pre-multiplied sums: 0 device
+ * memory, read by the kernel when it runs (stream-ordered); 1 host memory, read before the call returns.
+ * fp32 and fp16 denormals are kept; NaN payloads are unpinned.
+ * Validation, in this order: dtype not 6 / 9 (convert: an unsupported pair) 4; residence not 0 / 1 or NULL scalar
+ * 4; nsend outside 1..8 or NULL sends 4; count == 0 succeeds; NULL operand 4; chain: an operand partially
+ * overlapping dst 4 (own == dst and a source == dst are allowed); convert from fp32: src and dst sharing ANY byte
+ * 4; convert 16 -> 16: src == dst is allowed (in place), a partial overlap 4; launch failure 1.
+ * Placement as for the wide sum: the chain's 16-byte vector kernel for element-aligned operands in dst's 16-byte
+ * phase; the conversion's vector kernel when dst's 16-byte vectors and the source line up on 16-byte boundaries;
+ * any other placement takes an element-wise kernel kept for correctness.
+ */
+int dccl_local_reduce_chain_wide_scaled(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
+                                        size_t count, const void* scalar, int residence, void* stream);
+int dccl_local_convert_scaled(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count,
+                              const void* scalar, int residence, void* stream);
 
 /*
  * Multi-source device copy: dsts[y][0..bytes) = srcs[y][0..bytes) for y < npairs (<= 8), in one

@@ -92,6 +92,31 @@ static void cpu_checks(void) {
     CHECK(dccl_local_convert(c + 1, 7, c, 6, 4, NULL) == DCCL_INVALID_ARGUMENT); /* dst's second half in src */
     int wide_op = 0;
     CHECK(dccl_red_op_create_wide_sum(&wide_op, 9, NULL) == DCCL_INVALID_ARGUMENT); /* null communicator */
+    /* scaled wide sum: dtype, scalar / residence, nsend, count 0, NULL operands, overlap, in that order; the scalar
+     * is one float whatever the dtype */
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, a, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, a, b, 10, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, a, b, 9, 0, NULL, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, a, b, 9, 0, &half, 2, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 9, a, b, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(NULL, 1, a, b, 6, 4, &half, 0, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, NULL, NULL, 9, 0, &half, 0, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, NULL, b, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(ov, 1, a, c, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_wide_scaled(sends, 1, c + 1, c, 6, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    /* scaled conversion: 7 -> 6, 7 -> 9, 6 -> 6, 9 -> 9 only, scalar / residence, count 0, NULL operands, overlap */
+    CHECK(dccl_local_convert_scaled(a, 9, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(a, 6, b, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(a, 7, b, 7, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(a, 7, b, 9, 0, NULL, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(a, 9, b, 9, 0, &half, -1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(NULL, 7, NULL, 6, 0, &half, 1, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_convert_scaled(NULL, 7, b, 6, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(a, 6, NULL, 6, 4, &half, 0, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_convert_scaled(c, 7, c, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT);     /* no in-place */
+    CHECK(dccl_local_convert_scaled(c + 1, 9, c, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT); /* partial overlap */
+    CHECK(dccl_red_op_create_wide_scaled_sum(&wide_op, &half, 9, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null comm */
+    CHECK(dccl_red_op_create_wide_scaled_sum(&wide_op, &half, 9, 2, NULL) == DCCL_INVALID_ARGUMENT);
     /* batched row copy: every validation case answers before any device work (never-dereferenced addresses) */
     {
         char* const base = (char*)(uintptr_t)0x100000000000ull;
