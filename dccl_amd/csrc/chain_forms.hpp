@@ -51,4 +51,26 @@ int launch_chain_form(const void* const* sends, int nsend, const void* own, void
     });
 }
 
+// The placement rule of the one-source passes (premul.hip's scale, wide.hip's conversions).  `lead` is the side whose
+// 16-B vectors the vector kernel walks (elements of `lead_size` bytes: the destination of a scale, the 16-bit side of
+// a conversion), `other` the side it meets with elements of `other_size` bytes.  Head elements bring `lead` to an
+// `align`-byte boundary (16 or more, a power of two); `other` must be on a 16-B boundary there too (vec_ok), else the
+// element-wise kernel applies, ALIGNED when both sides are element-aligned (elem_ok).  `sp` counts in elements,
+// 16 / lead_size of them per vector; it is meaningful when vec_ok.
+struct PassPlacement {
+    bool elem_ok, vec_ok;
+    Split sp;
+};
+inline PassPlacement place_pass(uintptr_t lead, size_t lead_size, uintptr_t other, size_t other_size, size_t count,
+                                size_t align = 16) {
+    PassPlacement p{lead % lead_size == 0 && other % other_size == 0, false, {0, 0, 0}};
+    if (!p.elem_ok) return p;
+    size_t head = ((align - (lead & (align - 1))) & (align - 1)) / lead_size;
+    p.vec_ok = ((other + head * other_size) & 15) == 0;
+    if (head > count) head = count;
+    const size_t nvec = (count - head) / (16 / lead_size);
+    p.sp = Split{head, nvec, count - head - nvec * (16 / lead_size)};
+    return p;
+}
+
 }  // namespace dccl_amd

@@ -90,26 +90,31 @@ private:
     std::atomic<uint64_t> barrier_gen_{0};  // written under bmu_, polled without it
 };
 
-// A user op of a communicator: a pre-multiplied sum (ncclRedOpCreatePreMulSum), a wide sum (dcclRedOpCreateWideSum,
-// fp16 / bf16 accumulated in fp32; no scalar) or a scaled wide sum (dcclRedOpCreateWideScaledSum: the wide sum's
-// accumulator times one fp32 scalar, which bits / dev_ptr hold); handle = ncclNumOps + its slot.
-constexpr int kMaxUserOps = 16;
-enum UserOpKind : int { kPremulSum = 0, kWideSum = 1, kWideScaledSum = 2 };
-struct UserOp {
-    bool live = false;
-    int kind = kPremulSum;
-    int dtype = 0;
+// Which sum a reduction computes, from the op handle down to the chain launch.  `kind` alone says it:
+//   kBuiltin        a built-in op of dccl.hpp; no scalar
+//   kPremulSum      ncclRedOpCreatePreMulSum: the scalar is one element of the operands' dtype, times every operand
+//   kWideSum        dcclRedOpCreateWideSum: fp16 / bf16 accumulated in fp32, rounded once; no scalar
+//   kWideScaledSum  dcclRedOpCreateWideScaledSum: the scalar is ONE fp32, times the finished fp32 accumulator
+// Readers switch on `kind` or ask the accessor named for their question, never the scalar's storage.  A host-immediate
+// scalar lives in `bits`: a copy of the form (a queued call, a packed run) is complete, and its scalar() valid as long.
+enum SumKind : int { kBuiltin = 0, kPremulSum, kWideSum, kWideScaledSum };
+struct SumForm {
+    SumKind kind = kBuiltin;
     uint64_t bits = 0;              // the scalar's bytes, read at creation (ncclScalarHostImmediate)
     const void* dev_ptr = nullptr;  // ncclScalarDevice: read by each collective's kernels when they run
+    bool wide() const { return kind == kWideSum || kind == kWideScaledSum; }
+    bool has_scalar() const { return kind == kPremulSum || kind == kWideScaledSum; }
+    // the C entry points' (scalar, residence) pair
+    const void* scalar() const { return dev_ptr != nullptr ? dev_ptr : static_cast<const void*>(&bits); }
+    int residence() const { return dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate; }
 };
-// What a collective hands down for such an op: dccl_local_scale's (scalar, residence); scalar nullptr = none.
-// `wide`: a wide sum: the chain launch becomes dccl_local_reduce_chain_wide.  `wide` with a scalar: a scaled wide
-// sum; the scalar is then ONE fp32 that multiplies the finished accumulator (dccl_local_reduce_chain_wide_scaled,
-// dccl_local_convert_scaled) and never reaches the 16-bit pre-multiplication: every reader tests `wide` first.
-struct PremulArg {
-    const void* scalar = nullptr;
-    int residence = 0;
-    bool wide = false;
+
+// A user op of a communicator: a sum form of one dtype; handle = ncclNumOps + its slot.
+constexpr int kMaxUserOps = 16;
+struct UserOp {
+    bool live = false;
+    int dtype = 0;
+    SumForm form;
 };
 
 }  // namespace dccl_amd

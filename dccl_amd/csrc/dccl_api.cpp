@@ -85,31 +85,31 @@ ncclResult_t copy_bytes(void* dst, const void* src, size_t bytes, bool device, h
     return dccl::ncclSuccess;
 }
 
-// A pre-multiplied-sum handle that is live on `c` becomes (ncclSum, its scalar), a wide-sum handle (ncclSum, the
-// wide flag), a scaled-wide-sum handle (ncclSum, the wide flag and its fp32 scalar); every other op value keeps
-// today's answer (built-in ops, ncclAvg -> ncclInvalidUsage, anything
-// else -> ncclInvalidArgument).
-ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, PremulArg* pm) {
+// A user-op handle that is live on `c` becomes (ncclSum, a copy of its form); every other op value keeps today's
+// answer (built-in ops with the kBuiltin form, ncclAvg -> ncclInvalidUsage, anything else -> ncclInvalidArgument).
+ncclResult_t resolve_op(const dcclComm* c, int dtype, int* op, SumForm* form) {
     const int slot = *op - int(dccl::ncclNumOps);
     if (slot < 0 || slot >= kMaxUserOps || !c->user_ops[slot].live) return check_op_dtype(dtype, *op);
     const UserOp& u = c->user_ops[slot];
     if (u.dtype != dtype) return dccl::ncclInvalidArgument;
     *op = dccl::ncclSum;
-    pm->wide = u.kind != kPremulSum;
-    if (u.kind == kWideSum) return dccl::ncclSuccess;  // (ncclSum, wide flag): no scalar
-    pm->scalar = u.dev_ptr != nullptr ? u.dev_ptr : static_cast<const void*>(&u.bits);
-    pm->residence = u.dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate;
+    *form = u.form;
     return dccl::ncclSuccess;
 }
 
 // The collectives' first step outside the direct paths: dst = src, or dst = src * scalar for a pre-multiplied sum
-// (in place when src == dst), after which the algorithm runs with ncclSum.  A wide op never comes here (wide_staged
+// (in place when src == dst), after which the algorithm runs with ncclSum.  A wide form never comes here (wide_staged
 // takes it first): its scalar is an fp32 that multiplies the finished sum, not an element of `dtype`.
-ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, const PremulArg& pm, bool device,
+ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, const SumForm& form, bool device,
                          hipStream_t st) {
-    if (pm.wide) return dccl::ncclInternalError;
-    if (pm.scalar == nullptr) return copy_bytes(dst, src, count * size_of_dtype(dtype), device, st);
-    return static_cast<ncclResult_t>(dccl_local_scale(src, dst, dtype, count, pm.scalar, pm.residence, st));
+    switch (form.kind) {
+    case kBuiltin: return copy_bytes(dst, src, count * size_of_dtype(dtype), device, st);
+    case kPremulSum:
+        return static_cast<ncclResult_t>(dccl_local_scale(src, dst, dtype, count, form.scalar(), form.residence(), st));
+    case kWideSum:
+    case kWideScaledSum: break;
+    }
+    return dccl::ncclInternalError;
 }
 
 ncclResult_t placement(const void* send, const void* recv, bool* device) {
@@ -462,16 +462,34 @@ struct Call {
     void* recv = nullptr;
     size_t count = 0;          // as the call counts: recvcount for a reduce-scatter, sendcount for an all-gather
     int dtype = 0;
-    int user_op = 0;           // the op value as passed (a pre-multiplied-sum handle included): the run key
+    int user_op = 0;           // the op value as passed (a user-op handle included): the run key
     int op = 0;                // resolved: a built-in op
-    PremulArg pm;              // resolved: the pre-multiplied sum's scalar, the wide flag (with its scalar), or none
-    uint64_t bits = 0;         // a queued host-immediate scalar's own copy
+    SumForm form;              // resolved: which sum, with its scalar by value (comm.hpp)
     int root = 0;
     bool dev = false;
     Algorithm algo = Algorithm::kRing;  // ncclAllReduce: DCCL_ALLREDUCE_ALGORITHM when the call was validated
     hipStream_t stream = nullptr;
-    bool bits_live = false;
 };
+
+// The buffer checks every validator shares: the two buffers' one placement, a user op on device buffers only (its
+// scaling / widening kernels run on the GPU), and a transport that moves such buffers.
+ncclResult_t check_buffers(const dcclComm* comm, const void* a, const void* b, const SumForm& form, bool* dev) {
+    const ncclResult_t rc = placement(a, b, dev);
+    if (rc != ncclSuccess) return rc;
+    if (form.kind != kBuiltin && !*dev) return ncclInvalidUsage;
+    return transport_accepts(comm, *dev) ? ncclSuccess : ncclInvalidUsage;  // e.g. host buffers on RCCL / IPC
+}
+
+// The fields every collective has, by name; the validators write the rest where they learn it (user_op / op / form
+// from resolve_op, dev from check_buffers, root, algo).  Their `c` comes in default-constructed.
+void set_call(Call* c, int api, ncclComm_t comm, const void* send, void* recv, size_t count, int dtype) {
+    c->api = api;
+    c->comm = comm;
+    c->send = send;
+    c->recv = recv;
+    c->count = count;
+    c->dtype = dtype;
+}
 
 // ------------------------------------------------------------------------------------------
 // Every collective is "validate" (its checks, in their order, with their return values, unchanged; it leaves a
@@ -482,16 +500,12 @@ ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncc
                          ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
     validate_comm(comm, "ncclAllReduce");
     *todo = false;
-    int op = user_op;
-    PremulArg pm;
-    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
+    c->user_op = c->op = user_op;
+    ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
     if (count == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
-    bool dev = false;
-    if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
-    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;  // scaling / widening run on the GPU only
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;  // e.g. host buffers on RCCL / IPC
+    if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     const uint32_t W = comm->world;
     const Algorithm algo = allreduce_algorithm();  // dccl.cpp:412-413,454
     if (algo == Algorithm::kUnknown) return ncclInvalidUsage;
@@ -499,7 +513,8 @@ ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncc
     if (W > 1 && algo == Algorithm::kRabenseifner && count % (1u << floor_log2_u32(W)))
         return ncclInvalidArgument;  // all_reduce_recursive_halving_and_doubling.cpp:50-54
     if (W > 1 && algo != Algorithm::kRabenseifner && (count < W || count % W)) return ncclInvalidArgument;
-    *c = Call{group::kAllReduce, comm, sendbuff, recvbuff, count, datatype, user_op, op, pm, 0, 0, dev, algo, nullptr};
+    set_call(c, group::kAllReduce, comm, sendbuff, recvbuff, count, datatype);
+    c->algo = algo;
     *todo = true;
     return ncclSuccess;
 }
@@ -522,20 +537,20 @@ ncclResult_t ar_run(const Call& c, hipStream_t stream) {
     void* recvbuff = c.recv;
     const size_t count = c.count;
     const int datatype = c.dtype, op = c.op;
-    const PremulArg& pm = c.pm;
+    const SumForm& form = c.form;
     const bool dev = c.dev;
     const Algorithm algo = c.algo;
     const size_t total = count * size_of_dtype(datatype);
     const uint32_t W = comm->world;
     ncclResult_t rc;
     if (W > 1 && dev && direct_selected(comm))
-        return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, &pm);
+        return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, form);
     if (W > 1 && !dev && host_direct_selected(comm, total / W))
         return direct_all_reduce_host(comm, sendbuff, recvbuff, count, datatype, op);
-    if (pm.wide) return wide_staged(c, stream);
-    if (W > 1 && algo != Algorithm::kRabenseifner && !pm.wide && pm.scalar == nullptr && grouped_selected(comm, dev))
+    if (form.wide()) return wide_staged(c, stream);
+    if (W > 1 && algo != Algorithm::kRabenseifner && form.kind == kBuiltin && grouped_selected(comm, dev))
         return all_reduce_grouped(comm, sendbuff, recvbuff, count, datatype, op, stream);
-    rc = stage_input(recvbuff, sendbuff, count, datatype, pm, dev, stream);  // dccl.cpp:393-408
+    rc = stage_input(recvbuff, sendbuff, count, datatype, form, dev, stream);  // dccl.cpp:393-408
     if (rc != ncclSuccess) return rc;
     if (W == 1) return ncclSuccess;
     void* scratch = nullptr;
@@ -551,18 +566,13 @@ ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount,
                          ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
     validate_comm(comm, "ncclReduceScatter");
     *todo = false;
-    int op = user_op;
-    PremulArg pm;
-    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
+    c->user_op = c->op = user_op;
+    ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
     if (recvcount == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
-    bool dev = false;
-    if ((rc = placement(sendbuff, recvbuff, &dev)) != ncclSuccess) return rc;
-    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    *c = Call{group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype, user_op, op, pm, 0, 0, dev,
-              Algorithm::kRing, nullptr};
+    if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
+    set_call(c, group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype);
     *todo = true;
     return ncclSuccess;
 }
@@ -573,22 +583,22 @@ ncclResult_t rs_run(const Call& c, hipStream_t stream) {
     void* recvbuff = c.recv;
     const size_t recvcount = c.count;
     const int datatype = c.dtype, op = c.op;
-    const PremulArg& pm = c.pm;
+    const SumForm& form = c.form;
     const bool dev = c.dev;
     ncclResult_t rc;
     const uint32_t W = comm->world, r = comm->rank;
     const size_t slot = recvcount * size_of_dtype(datatype), total = slot * W;
     if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream, &pm);
+        return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream, form);
     if (W > 1 && !dev && host_direct_selected(comm, slot))
         return direct_reduce_scatter_host(comm, sendbuff, recvbuff, recvcount, datatype, op);
-    if (pm.wide) return wide_staged(c, stream);
+    if (form.wide()) return wide_staged(c, stream);
     // slot r, reduced straight from sendbuff: no work copy (a pre-multiplied sum scales into the work copy: the ring)
-    if (W > 1 && !pm.wide && pm.scalar == nullptr && grouped_selected(comm, dev))
+    if (W > 1 && form.kind == kBuiltin && grouped_selected(comm, dev))
         return reduce_scatter_grouped(comm, sendbuff, recvbuff, recvcount * W, datatype, op, stream, 0);
     if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
     void* work = dev ? comm->dev_work : comm->host_work;
-    rc = stage_input(work, sendbuff, recvcount * W, datatype, pm, dev, stream);  // dccl.cpp:585-609
+    rc = stage_input(work, sendbuff, recvcount * W, datatype, form, dev, stream);  // dccl.cpp:585-609
     if (rc != ncclSuccess) return rc;
     if (W > 1) {
         void* scratch = nullptr;
@@ -605,9 +615,8 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
                              ncclRedOp_t user_op, int root, ncclComm_t comm, Call* c, bool* todo) {
     validate_comm(comm, "ncclReduce");
     *todo = false;
-    int op = user_op;
-    PremulArg pm;
-    ncclResult_t rc = resolve_op(comm, datatype, &op, &pm);
+    c->user_op = c->op = user_op;
+    ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
     const uint32_t W = comm->world, r = comm->rank;
     if (root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
@@ -615,12 +624,9 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
     if (count % W) return ncclInvalidArgument;  // dccl.cpp:762-767
     const bool iamroot = r == uint32_t(root);
     if (sendbuff == nullptr || (iamroot && recvbuff == nullptr)) return ncclInvalidArgument;
-    bool dev = false;
-    if ((rc = placement(sendbuff, iamroot ? recvbuff : sendbuff, &dev)) != ncclSuccess) return rc;
-    if ((pm.scalar != nullptr || pm.wide) && !dev) return ncclInvalidUsage;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    *c = Call{group::kReduce, comm, sendbuff, recvbuff, count, datatype, user_op, op, pm, 0, root, dev,
-              Algorithm::kRing, nullptr};
+    if ((rc = check_buffers(comm, sendbuff, iamroot ? recvbuff : sendbuff, c->form, &c->dev)) != ncclSuccess) return rc;
+    set_call(c, group::kReduce, comm, sendbuff, recvbuff, count, datatype);
+    c->root = root;
     *todo = true;
     return ncclSuccess;
 }
@@ -631,21 +637,21 @@ ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
     void* recvbuff = c.recv;
     const size_t count = c.count;
     const int datatype = c.dtype, op = c.op, root = c.root;
-    const PremulArg& pm = c.pm;
+    const SumForm& form = c.form;
     const bool dev = c.dev;
     ncclResult_t rc;
     const uint32_t W = comm->world, r = comm->rank;
     const bool iamroot = r == uint32_t(root);
     if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, &pm);
-    if (pm.wide) return wide_staged(c, stream);
+        return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, form);
+    if (form.wide()) return wide_staged(c, stream);
     const size_t total = count * size_of_dtype(datatype), slot = total / W;
     void* rbuf = recvbuff;
     if (!iamroot) {
         if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
         rbuf = dev ? comm->dev_work : comm->host_work;
     }
-    if ((rc = stage_input(rbuf, sendbuff, count, datatype, pm, dev, stream)) != ncclSuccess) return rc;
+    if ((rc = stage_input(rbuf, sendbuff, count, datatype, form, dev, stream)) != ncclSuccess) return rc;
     if (W == 1) return ncclSuccess;
     void* scratch = nullptr;
     if ((rc = ring_scratch(comm, slot, dev, &scratch)) != ncclSuccess) return rc;
@@ -683,12 +689,9 @@ ncclResult_t ag_validate(const void* sendbuff, void* recvbuff, size_t sendcount,
     if (esz == 0) return ncclInvalidArgument;
     if (sendcount == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
-    bool dev = false;
-    ncclResult_t rc = placement(sendbuff, recvbuff, &dev);
+    const ncclResult_t rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev);
     if (rc != ncclSuccess) return rc;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    *c = Call{group::kAllGather, comm, sendbuff, recvbuff, sendcount, datatype, 0, 0, PremulArg{}, 0, 0, dev,
-              Algorithm::kRing, nullptr};
+    set_call(c, group::kAllGather, comm, sendbuff, recvbuff, sendcount, datatype);
     *todo = true;
     return ncclSuccess;
 }
@@ -713,12 +716,10 @@ ncclResult_t bcast_validate(const void* sendbuff, void* recvbuff, size_t count, 
     const uint32_t W = comm->world, r = comm->rank;
     if (esz == 0 || root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
     if (count == 0) return ncclSuccess;
-    bool dev = false;
-    ncclResult_t rc = placement(r == uint32_t(root) ? sendbuff : recvbuff, recvbuff, &dev);
+    const ncclResult_t rc = check_buffers(comm, r == uint32_t(root) ? sendbuff : recvbuff, recvbuff, c->form, &c->dev);
     if (rc != ncclSuccess) return rc;
-    if (!transport_accepts(comm, dev)) return ncclInvalidUsage;
-    *c = Call{group::kBroadcast, comm, sendbuff, recvbuff, count, datatype, 0, 0, PremulArg{}, 0, root, dev,
-              Algorithm::kRing, nullptr};
+    set_call(c, group::kBroadcast, comm, sendbuff, recvbuff, count, datatype);
+    c->root = root;
     *todo = true;
     return ncclSuccess;
 }
@@ -771,7 +772,7 @@ ncclResult_t run_plain(const Call& c) {
 // fp32 staging buffer, run the ncclFloat32 / ncclSum collective these settings select on it (ring, Rabenseifner,
 // p2p, RCCL ring or grouped), and round its result once into recvbuff (ncclReduce: on the root only).  A
 // reduce-scatter's fp32 result lies behind the widened input.  The staging buffer is not dev_work: rs_run and
-// reduce_run grow that one underneath.  W == 1: the input's bytes.  A scaled wide sum (c.pm.scalar, one fp32)
+// reduce_run grow that one underneath.  W == 1: the input's bytes.  A scaled wide sum (kWideScaledSum, one fp32)
 // takes the same route with dccl_local_convert_scaled as the narrowing pass, which multiplies as it rounds; the
 // fp32 collective in the middle never sees the scalar.  Its W == 1 is that pass from 16 bits to 16 bits.
 ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
@@ -780,10 +781,11 @@ ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
     const bool rs = c.api == group::kReduceScatter;
     const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
     const bool has_out = c.api != group::kReduce || comm->rank == uint32_t(c.root);
-    const PremulArg& pm = c.pm;
-    if (W == 1 && pm.scalar != nullptr)
-        return static_cast<ncclResult_t>(
-            dccl_local_convert_scaled(c.send, c.dtype, c.recv, c.dtype, out_count, pm.scalar, pm.residence, stream));
+    const SumForm& form = c.form;  // kWideSum or kWideScaledSum: the callers test form.wide()
+    const bool scaled = form.kind == kWideScaledSum;
+    if (W == 1 && scaled)
+        return static_cast<ncclResult_t>(dccl_local_convert_scaled(c.send, c.dtype, c.recv, c.dtype, out_count,
+                                                                   form.scalar(), form.residence(), stream));
     if (W == 1) return copy_bytes(c.recv, c.send, out_count * size_of_dtype(c.dtype), true, stream);
     ncclResult_t rc = ensure_wide(comm, (in_count + (rs ? out_count : 0)) * sizeof(float));
     if (rc != ncclSuccess) return rc;
@@ -795,13 +797,13 @@ ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
     f.recv = rs ? wide + in_count : wide;
     f.dtype = ncclFloat32;
     f.op = ncclSum;
-    f.pm = PremulArg{};
+    f.form = SumForm{};
     f.stream = stream;
     rc = run_plain(f);
     if (rc != ncclSuccess || !has_out) return rc;
-    if (pm.scalar != nullptr)
+    if (scaled)
         return static_cast<ncclResult_t>(dccl_local_convert_scaled(f.recv, ncclFloat32, c.recv, c.dtype, out_count,
-                                                                   pm.scalar, pm.residence, stream));
+                                                                   form.scalar(), form.residence(), stream));
     return static_cast<ncclResult_t>(dccl_local_convert(f.recv, ncclFloat32, c.recv, c.dtype, out_count, stream));
 }
 
@@ -828,16 +830,10 @@ size_t coalesce_max_bytes() {
     return group::kDefaultMaxBytes;
 }
 
-// Inside a group: a validated call joins the queue.  The scalar of a host-immediate pre-multiplied sum (or scaled
-// wide sum: one fp32 inside the same 8 bytes) is kept in the entry itself (run_queue points the entry's PremulArg
-// at it), so nothing refers to the op's slot later.
+// Inside a group: a validated call joins the queue.  Its SumForm holds a host-immediate scalar by value, so nothing
+// refers to the op's slot later: the op may be destroyed, and its slot taken again, before the group ends.
 ncclResult_t enqueue(Call c, hipStream_t stream) {
     c.stream = stream;
-    if (c.pm.scalar != nullptr && c.pm.residence == ncclScalarHostImmediate) {
-        std::memcpy(&c.bits, c.pm.scalar, sizeof c.bits);
-        c.pm.scalar = nullptr;  // set again when the entry has its final address
-        c.bits_live = true;
-    }
     tl_queue.push_back(c);
     g_group_stats[1].fetch_add(1, std::memory_order_relaxed);
     return ncclSuccess;
@@ -926,9 +922,7 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
 
 // The outermost ncclGroupEnd: every queued item executes, in issue order, even after an error (a collective
 // never leaves a peer waiting); the first error is returned.
-ncclResult_t run_queue(std::vector<Call>& q) {
-    for (Call& c : q)
-        if (c.bits_live) c.pm.scalar = &c.bits;
+ncclResult_t run_queue(const std::vector<Call>& q) {
     std::vector<group::Call> plan(q.size());
     for (size_t i = 0; i < q.size(); ++i) {
         const Call& c = q[i];
@@ -955,6 +949,26 @@ ncclResult_t run_queue(std::vector<Call>& q) {
         }
     }
     return first;
+}
+
+// The first free slot of the communicator's op table becomes a `kind` op of `datatype`; its scalar (`scalar_bytes`
+// of it, none for 0) is read now from the host or kept as a device address.  The public create functions check
+// their own arguments first.
+ncclResult_t create_user_op(ncclComm_t comm, SumKind kind, int datatype, const void* scalar, int residence,
+                            size_t scalar_bytes, ncclRedOp_t* out) {
+    for (int slot = 0; slot < kMaxUserOps; ++slot) {
+        UserOp& u = comm->user_ops[slot];
+        if (u.live) continue;
+        u = UserOp{};
+        u.live = true;
+        u.dtype = datatype;
+        u.form.kind = kind;
+        if (scalar_bytes != 0 && residence == ncclScalarDevice) u.form.dev_ptr = scalar;
+        else if (scalar_bytes != 0) std::memcpy(&u.form.bits, scalar, scalar_bytes);
+        *out = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
+        return ncclSuccess;
+    }
+    return ncclInvalidUsage;  // kMaxUserOps live ops already
 }
 
 }  // namespace
@@ -1008,35 +1022,14 @@ ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataTyp
     const size_t esz = size_of_dtype(datatype);
     if (op == nullptr || scalar == nullptr || esz == 0) return ncclInvalidArgument;
     if (residence != ncclScalarDevice && residence != ncclScalarHostImmediate) return ncclInvalidArgument;
-    for (int slot = 0; slot < kMaxUserOps; ++slot) {
-        UserOp& u = comm->user_ops[slot];
-        if (u.live) continue;
-        u = UserOp{};
-        u.live = true;
-        u.dtype = datatype;
-        if (residence == ncclScalarDevice) u.dev_ptr = scalar;
-        else std::memcpy(&u.bits, scalar, esz);
-        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
-        return ncclSuccess;
-    }
-    return ncclInvalidUsage;  // kMaxUserOps live ops already
+    return create_user_op(comm, kPremulSum, datatype, scalar, residence, esz, op);
 }
 
 ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, ncclComm_t comm) {
     validate_comm(comm, __func__);
     if (op == nullptr) return ncclInvalidArgument;
     if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
-    for (int slot = 0; slot < kMaxUserOps; ++slot) {
-        UserOp& u = comm->user_ops[slot];
-        if (u.live) continue;
-        u = UserOp{};
-        u.live = true;
-        u.kind = kWideSum;
-        u.dtype = datatype;
-        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
-        return ncclSuccess;
-    }
-    return ncclInvalidUsage;  // kMaxUserOps live ops already
+    return create_user_op(comm, kWideSum, datatype, nullptr, ncclScalarHostImmediate, 0, op);
 }
 
 ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, ncclDataType_t datatype,
@@ -1045,19 +1038,8 @@ ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, n
     if (op == nullptr || scalar == nullptr) return ncclInvalidArgument;
     if (residence != ncclScalarDevice && residence != ncclScalarHostImmediate) return ncclInvalidArgument;
     if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
-    for (int slot = 0; slot < kMaxUserOps; ++slot) {
-        UserOp& u = comm->user_ops[slot];
-        if (u.live) continue;
-        u = UserOp{};
-        u.live = true;
-        u.kind = kWideScaledSum;
-        u.dtype = datatype;
-        if (residence == ncclScalarDevice) u.dev_ptr = scalar;
-        else std::memcpy(&u.bits, scalar, sizeof(float));  // always one fp32, whatever the datatype
-        *op = static_cast<ncclRedOp_t>(int(ncclNumOps) + slot);
-        return ncclSuccess;
-    }
-    return ncclInvalidUsage;  // kMaxUserOps live ops already
+    // always one fp32, whatever the datatype
+    return create_user_op(comm, kWideScaledSum, datatype, scalar, residence, sizeof(float), op);
 }
 
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
@@ -1213,37 +1195,42 @@ extern "C" int dccl_broadcast(const void* send, void* recv, size_t count, int dt
     });
 }
 
-extern "C" int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm) {
-    if (residence != 0 && residence != 1) return DCCL_INVALID_ARGUMENT;  // before the cast to the two-value enum
+namespace {
+// The create functions' handle out-parameter for a C caller: `create` gets a ncclRedOp_t* (null when `op` is), and
+// *op is written on success only.
+template <typename F>
+int create_handle(int* op, F&& create) {
     return guarded([&] {
         dccl::ncclRedOp_t h = dccl::ncclSum;
-        const ncclResult_t rc = dccl::ncclRedOpCreatePreMulSum(
-            op != nullptr ? &h : nullptr, const_cast<void*>(scalar), static_cast<dccl::ncclDataType_t>(dtype),
-            static_cast<dccl::ncclScalarResidence_t>(residence), static_cast<dccl::ncclComm_t>(comm));
+        const ncclResult_t rc = create(op != nullptr ? &h : nullptr);
         if (rc == dccl::ncclSuccess) *op = int(h);
         return rc;
     });
 }
+}  // namespace
+
+extern "C" int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int residence, void* comm) {
+    if (residence != 0 && residence != 1) return DCCL_INVALID_ARGUMENT;  // before the cast to the two-value enum
+    return create_handle(op, [&](dccl::ncclRedOp_t* h) {
+        return dccl::ncclRedOpCreatePreMulSum(h, const_cast<void*>(scalar), static_cast<dccl::ncclDataType_t>(dtype),
+                                              static_cast<dccl::ncclScalarResidence_t>(residence),
+                                              static_cast<dccl::ncclComm_t>(comm));
+    });
+}
 
 extern "C" int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm) {
-    return guarded([&] {
-        dccl::ncclRedOp_t h = dccl::ncclSum;
-        const ncclResult_t rc = dccl::dcclRedOpCreateWideSum(
-            op != nullptr ? &h : nullptr, static_cast<dccl::ncclDataType_t>(dtype), static_cast<dccl::ncclComm_t>(comm));
-        if (rc == dccl::ncclSuccess) *op = int(h);
-        return rc;
+    return create_handle(op, [&](dccl::ncclRedOp_t* h) {
+        return dccl::dcclRedOpCreateWideSum(h, static_cast<dccl::ncclDataType_t>(dtype),
+                                            static_cast<dccl::ncclComm_t>(comm));
     });
 }
 
 extern "C" int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, int dtype, int residence, void* comm) {
     if (residence != 0 && residence != 1) return DCCL_INVALID_ARGUMENT;  // before the cast to the two-value enum
-    return guarded([&] {
-        dccl::ncclRedOp_t h = dccl::ncclSum;
-        const ncclResult_t rc = dccl::dcclRedOpCreateWideScaledSum(
-            op != nullptr ? &h : nullptr, scalar, static_cast<dccl::ncclDataType_t>(dtype),
-            static_cast<dccl::ncclScalarResidence_t>(residence), static_cast<dccl::ncclComm_t>(comm));
-        if (rc == dccl::ncclSuccess) *op = int(h);
-        return rc;
+    return create_handle(op, [&](dccl::ncclRedOp_t* h) {
+        return dccl::dcclRedOpCreateWideScaledSum(h, scalar, static_cast<dccl::ncclDataType_t>(dtype),
+                                                  static_cast<dccl::ncclScalarResidence_t>(residence),
+                                                  static_cast<dccl::ncclComm_t>(comm));
     });
 }
 

@@ -625,26 +625,26 @@ ncclResult_t exchange(dcclComm* c, Publish* pub, hipStream_t st, Peers* P, bool*
 // dst = the ring's combine chain for one chunk: contributions of ranks first, first+1, ...,
 // first+W-2 (their `in` buffers at byte offset `off`), then `own` last.
 ncclResult_t chain(const Peers& P, uint32_t W, uint32_t first, size_t off, const void* own, void* dst, size_t elems,
-                   int dtype, int op, hipStream_t st, uint32_t rank, const PremulArg* pm) {
+                   int dtype, int op, hipStream_t st, uint32_t rank, const SumForm& form) {
     if (fault_injected("direct_combine", rank)) return dccl::ncclUnhandledCudaError;
     const void* sends[kDirectMaxWorld];
     for (uint32_t j = 0; j + 1 < W; ++j) sends[j] = P.in[(first + j) % W] + off;
-    // `pm` wide: a wide sum (fp16 / bf16, op is ncclSum), the same chain accumulated in fp32 and rounded once; with
-    // a scalar (one fp32) the accumulator is multiplied by it before that rounding.  Tested before the scalar alone:
-    // a wide op's scalar must never reach the 16-bit pre-multiplication.
-    if (pm != nullptr && pm->wide) {
-        if (pm->scalar != nullptr)
-            return static_cast<ncclResult_t>(dccl_local_reduce_chain_wide_scaled(
-                sends, int(W - 1), own, dst, dtype, elems, pm->scalar, pm->residence, static_cast<void*>(st)));
-        return static_cast<ncclResult_t>(
-            dccl_local_reduce_chain_wide(sends, int(W - 1), own, dst, dtype, elems, static_cast<void*>(st)));
+    const int k = int(W - 1);
+    void* s = static_cast<void*>(st);
+    int rc = DCCL_INTERNAL_ERROR;
+    switch (form.kind) {  // comm.hpp SumForm: one chain entry point per kind; op is ncclSum for all but kBuiltin
+    case kBuiltin: rc = dccl_local_reduce_chain(sends, k, own, dst, dtype, elems, op, s); break;
+    case kPremulSum:  // every operand scaled as it is read
+        rc = dccl_local_reduce_chain_premul(sends, k, own, dst, dtype, elems, form.scalar(), form.residence(), s);
+        break;
+    case kWideSum:  // fp16 / bf16 accumulated in fp32, rounded once
+        rc = dccl_local_reduce_chain_wide(sends, k, own, dst, dtype, elems, s);
+        break;
+    case kWideScaledSum:  // the fp32 accumulator times one fp32 scalar before that rounding
+        rc = dccl_local_reduce_chain_wide_scaled(sends, k, own, dst, dtype, elems, form.scalar(), form.residence(), s);
+        break;
     }
-    // `pm` with a scalar: a pre-multiplied sum (op is ncclSum), the same chain with every operand scaled as it is read
-    if (pm != nullptr && pm->scalar != nullptr)
-        return static_cast<ncclResult_t>(dccl_local_reduce_chain_premul(
-            sends, int(W - 1), own, dst, dtype, elems, pm->scalar, pm->residence, static_cast<void*>(st)));
-    return static_cast<ncclResult_t>(
-        dccl_local_reduce_chain(sends, int(W - 1), own, dst, dtype, elems, op, static_cast<void*>(st)));
+    return static_cast<ncclResult_t>(rc);
 }
 
 ncclResult_t copy_pairs(const std::vector<const void*>& src, const std::vector<void*>& dst, size_t bytes,
@@ -876,7 +876,7 @@ bool direct_selected(const dcclComm* c) {
 // `recv` is replaced by the scratch for the reduced chunk (reduced in
 // place there: no other rank reads that chunk of anyone's input), which this rank then copies out.
 ncclResult_t direct_all_reduce(dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
-                               hipStream_t st, const PremulArg* pm) {
+                               hipStream_t st, const SumForm& form) {
     const uint32_t W = c->world, r = c->rank;
     if (W > kDirectMaxWorld) return dccl::ncclInvalidUsage;
     const size_t esz = size_of_dtype(dtype), slot_elems = count / W, slot = slot_elems * esz, total = count * esz;
@@ -892,7 +892,7 @@ ncclResult_t direct_all_reduce(dcclComm* c, const void* send, void* recv, size_t
     const uint32_t mine = (r + 1) % W;
     if (rc == dccl::ncclSuccess)
         rc = chain(P, W, mine, mine * slot, P.in[r] + mine * slot, P.out[r] + mine * slot, slot_elems, dtype, op, st, r,
-                   pm);
+                   form);
     if ((rc = arrive(c, st, rc)) != dccl::ncclSuccess) return rc;  // every chunk reduced by its owner
     std::vector<const void*> src;
     std::vector<void*> dst;
@@ -969,7 +969,7 @@ ncclResult_t direct_reduce_scatter_host(dcclComm* c, const void* send, void* rec
 // ncclReduceScatter: the ring with rank maps (o+W-1)%W / (n+1)%W (dccl.cpp:551-698) leaves slot o on
 // rank o, combined in the order o+1, o+2, ..., o-1, o.
 ncclResult_t direct_reduce_scatter(dcclComm* c, const void* send, void* recv, size_t recvcount, int dtype, int op,
-                                   hipStream_t st, const PremulArg* pm) {
+                                   hipStream_t st, const SumForm& form) {
     const uint32_t W = c->world, r = c->rank;
     if (W > kDirectMaxWorld) return dccl::ncclInvalidUsage;
     const size_t slot = recvcount * size_of_dtype(dtype);
@@ -981,14 +981,14 @@ ncclResult_t direct_reduce_scatter(dcclComm* c, const void* send, void* recv, si
     ncclResult_t rc = exchange(c, &pub, st, &P, &met);
     if (!met) return rc;
     if (rc == dccl::ncclSuccess)
-        rc = chain(P, W, (r + 1) % W, r * slot, P.in[r] + r * slot, recv, recvcount, dtype, op, st, r, pm);
+        rc = chain(P, W, (r + 1) % W, r * slot, P.in[r] + r * slot, recv, recvcount, dtype, op, st, r, form);
     return arrive(c, st, rc, &P);
 }
 
 // ncclReduce: the reference runs the reduce-scatter ring with the same maps, then gathers the slots
 // at the root (dccl.cpp:745-846); here the root reduces every slot itself.
 ncclResult_t direct_reduce(dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op, uint32_t root,
-                           hipStream_t st, const PremulArg* pm) {
+                           hipStream_t st, const SumForm& form) {
     const uint32_t W = c->world, r = c->rank;
     if (W > kDirectMaxWorld) return dccl::ncclInvalidUsage;
     const size_t slot_elems = count / W, slot = slot_elems * size_of_dtype(dtype);
@@ -1002,7 +1002,7 @@ ncclResult_t direct_reduce(dcclComm* c, const void* send, void* recv, size_t cou
     if (r == root)
         for (uint32_t o = 0; o < W && rc == dccl::ncclSuccess; ++o)
             rc = chain(P, W, (o + 1) % W, o * slot, P.in[o] + o * slot, static_cast<unsigned char*>(recv) + o * slot,
-                       slot_elems, dtype, op, st, r, pm);
+                       slot_elems, dtype, op, st, r, form);
     return arrive(c, st, rc, &P);
 }
 

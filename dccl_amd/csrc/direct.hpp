@@ -48,12 +48,12 @@ int ipc_stats(uint64_t* out, int n);
 // rabenseifner.
 bool direct_selected(const dccl::dcclComm* c);
 
-// `pm` (here and in direct_reduce_scatter / direct_reduce): a pre-multiplied sum (comm.hpp PremulArg; op is
-// ncclSum then): the chain launch multiplies every contribution by the scalar as it reads it.  With pm->wide (a
-// wide sum, fp16 / bf16) the chain launch accumulates in fp32 and rounds once; the bytes moved are unchanged.  With
-// pm->wide and a scalar (a scaled wide sum) the scalar is one fp32 that multiplies the accumulator before the rounding.
+// `form` (here and in direct_reduce_scatter / direct_reduce): which sum the chain launch computes (comm.hpp SumForm;
+// op is ncclSum for every kind but kBuiltin).  kPremulSum multiplies every contribution by the scalar as it reads it;
+// kWideSum (fp16 / bf16) accumulates in fp32 and rounds once, the bytes moved unchanged; kWideScaledSum multiplies that
+// accumulator by its one fp32 scalar before the rounding.
 ncclResult_t direct_all_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
-                               hipStream_t st, const PremulArg* pm = nullptr);
+                               hipStream_t st, const SumForm& form);
 
 // Host buffers of an in-process group: the direct all_reduce with the chain combine staged through the
 // GPU (dccl_local_reduce_chain_host, staged in double-buffered pieces) and the all-gather by memcpy from
@@ -64,9 +64,9 @@ ncclResult_t direct_all_reduce_host(dccl::dcclComm* c, const void* send, void* r
 ncclResult_t direct_reduce_scatter_host(dccl::dcclComm* c, const void* send, void* recv, size_t recvcount,
                                         int dtype, int op);
 ncclResult_t direct_reduce_scatter(dccl::dcclComm* c, const void* send, void* recv, size_t recvcount, int dtype,
-                                   int op, hipStream_t st, const PremulArg* pm = nullptr);
+                                   int op, hipStream_t st, const SumForm& form);
 ncclResult_t direct_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
-                           uint32_t root, hipStream_t st, const PremulArg* pm = nullptr);
+                           uint32_t root, hipStream_t st, const SumForm& form);
 ncclResult_t direct_all_gather(dccl::dcclComm* c, const void* send, void* recv, size_t sendcount, int dtype,
                                hipStream_t st);
 ncclResult_t direct_broadcast(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype,

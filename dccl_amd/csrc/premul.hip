@@ -133,15 +133,16 @@ template <typename T>
 int scale_typed(const void* src, void* dst, size_t count, ScalarArg sa, hipStream_t stream) {
     auto s = static_cast<const unsigned char*>(src);
     auto d = static_cast<unsigned char*>(dst);
-    const uintptr_t as = reinterpret_cast<uintptr_t>(src), ad = reinterpret_cast<uintptr_t>(dst);
-    if (as % sizeof(T) || ad % sizeof(T) || ((as ^ ad) & 15)) {
+    // chain_forms.hpp place_pass: dst leads, to its 128-B lines; src (same element size) must share its 16-B phase
+    PassPlacement p = place_pass(reinterpret_cast<uintptr_t>(dst), sizeof(T), reinterpret_cast<uintptr_t>(src),
+                                 sizeof(T), count, kDstAlign);
+    if (!p.vec_ok) {
         void* args[] = {&s, &d, &count, &sa};
-        const void* fn = (as % sizeof(T) || ad % sizeof(T))
-                             ? reinterpret_cast<const void*>(&scale_elem_kernel<T, false>)
-                             : reinterpret_cast<const void*>(&scale_elem_kernel<T, true>);
+        const void* fn = !p.elem_ok ? reinterpret_cast<const void*>(&scale_elem_kernel<T, false>)
+                                    : reinterpret_cast<const void*>(&scale_elem_kernel<T, true>);
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
-    Split sp = split_for_vectors<T>(ad, count, kDstAlign);
+    Split& sp = p.sp;
     void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail, &sa};
     return launch(reinterpret_cast<const void*>(&scale_vec_kernel<T>), grid_for(sp, 64), args, stream, 64);
 }

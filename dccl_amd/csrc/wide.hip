@@ -75,18 +75,6 @@ __device__ __forceinline__ F32x8 add16(u32x4 v, F32x8 acc) {
     return acc;
 }
 
-// The chain policy (reduce_kernels.hpp chain_vec_body): fp32 accumulators, rounded to 16 bits at the store.
-template <typename T>
-struct WideChain {
-    using Elem = T;
-    __device__ __forceinline__ F32x8 first16(u32x4 v) const { return widen16<T>(v); }
-    __device__ __forceinline__ F32x8 fold16(u32x4 v, F32x8 acc) const { return add16<T>(v, acc); }
-    __device__ __forceinline__ u32x4 finish16(const F32x8& acc) const { return narrow16<T>(acc); }
-    __device__ __forceinline__ float first(T x) const { return Wide<T>::widen(x); }
-    __device__ __forceinline__ float fold(T x, float acc) const { return Wide<T>::widen(x) + acc; }
-    __device__ __forceinline__ T finish(float acc) const { return Wide<T>::narrow(acc); }
-};
-
 // acc * s on its way to the 16-bit rounding of ONE element (edge elements, element-wise kernels): one IEEE fp32
 // multiply, rounded to fp32 (no contraction: nothing may fuse it with an add of the chain).  For fp16 the product
 // then passes an identity lane move (every lane reads itself).  Without it hipcc selects v_fma_mixlo_f16 /
@@ -125,18 +113,35 @@ __device__ __forceinline__ u32x4 narrow_scaled16(const F32x8& acc, float s) {
     }
 }
 
-// WideChain carrying the fp32 scalar: the finished accumulators are multiplied by s, then rounded once.
-template <typename T>
-struct WideScaledChain {
-    using Elem = T;
+// How the finished fp32 accumulators become 16 bits: rounded as they are, or multiplied by the fp32 scalar s first.
+struct NoScale {
+    template <typename T>
+    __device__ __forceinline__ u32x4 finish16(const F32x8& acc) const { return narrow16<T>(acc); }
+    template <typename T>
+    __device__ __forceinline__ T finish(float acc) const { return Wide<T>::narrow(acc); }
+};
+struct ScaleBy {
     float s;
-    __device__ __forceinline__ F32x8 first16(u32x4 v) const { return widen16<T>(v); }
-    __device__ __forceinline__ F32x8 fold16(u32x4 v, F32x8 acc) const { return add16<T>(v, acc); }
+    template <typename T>
     __device__ __forceinline__ u32x4 finish16(const F32x8& acc) const { return narrow_scaled16<T>(acc, s); }
-    __device__ __forceinline__ float first(T x) const { return Wide<T>::widen(x); }
-    __device__ __forceinline__ float fold(T x, float acc) const { return Wide<T>::widen(x) + acc; }
+    template <typename T>
     __device__ __forceinline__ T finish(float acc) const { return Wide<T>::narrow(scale1<T>(acc, s)); }
 };
+
+// The chain policy (reduce_kernels.hpp chain_vec_body): fp32 accumulators, rounded to 16 bits once, at the store.
+template <typename T, typename Scale = NoScale>
+struct WideChain {
+    using Elem = T;
+    Scale scale;
+    __device__ __forceinline__ F32x8 first16(u32x4 v) const { return widen16<T>(v); }
+    __device__ __forceinline__ F32x8 fold16(u32x4 v, F32x8 acc) const { return add16<T>(v, acc); }
+    __device__ __forceinline__ u32x4 finish16(const F32x8& acc) const { return scale.template finish16<T>(acc); }
+    __device__ __forceinline__ float first(T x) const { return Wide<T>::widen(x); }
+    __device__ __forceinline__ float fold(T x, float acc) const { return Wide<T>::widen(x) + acc; }
+    __device__ __forceinline__ T finish(float acc) const { return scale.template finish<T>(acc); }
+};
+template <typename T>
+using WideScaledChain = WideChain<T, ScaleBy>;
 
 // ---- chain: reduce_chain_vec_kernel's roles and order, one fp32 accumulator per element ----
 template <typename T, int K, typename C>
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(C::BLOCK) void wide_scaled_chain_vec_kernel(SendLis
                                                                          unsigned char* dst, size_t head, size_t nvec,
                                                                          size_t tail, ScalarArg sa) {
     chain_vec_body<WideScaledChain<T>, K, C>(sends, own, dst, head, nvec, tail,
-                                             WideScaledChain<T>{load_scalar<float>(sa)});
+                                             WideScaledChain<T>{{load_scalar<float>(sa)}});
 }
 
 template <typename T, bool ALIGNED>
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void wide_scaled_chain_elem_kernel(SendList
                                                                         const unsigned char* own, unsigned char* dst,
                                                                         size_t count, ScalarArg sa) {
     chain_elem_body<WideScaledChain<T>, ALIGNED>(sends, nsend, own, dst, count,
-                                                 WideScaledChain<T>{load_scalar<float>(sa)});
+                                                 WideScaledChain<T>{{load_scalar<float>(sa)}});
 }
 
 // ---- convert: `half` is the 16-bit side, `full` the fp32 side; WIDEN: half -> full, else full -> half ----
@@ -271,41 +276,34 @@ int convert_typed(const void* src, void* dst, size_t count, hipStream_t stream) 
     auto s = static_cast<const unsigned char*>(src);
     auto d = static_cast<unsigned char*>(dst);
     const uintptr_t as = reinterpret_cast<uintptr_t>(src), ad = reinterpret_cast<uintptr_t>(dst);
-    const uintptr_t half = WIDEN ? as : ad, full = WIDEN ? ad : as;
-    const bool elem_ok = half % sizeof(T) == 0 && full % sizeof(float) == 0;
-    // head elements bring the 16-bit side to a 16-B boundary; the fp32 side must be on one there too
-    size_t head = elem_ok ? ((16 - (half & 15)) & 15) / sizeof(T) : 0;
-    if (!elem_ok || ((full + head * sizeof(float)) & 15)) {
+    // chain_forms.hpp place_pass: the 16-bit side leads, the fp32 side must meet its 16-B vectors
+    PassPlacement p = WIDEN ? place_pass(as, sizeof(T), ad, sizeof(float), count)
+                            : place_pass(ad, sizeof(T), as, sizeof(float), count);
+    if (!p.vec_ok) {
         void* args[] = {&s, &d, &count};
-        const void* fn = elem_ok ? reinterpret_cast<const void*>(&convert_elem_kernel<T, WIDEN, true>)
-                                 : reinterpret_cast<const void*>(&convert_elem_kernel<T, WIDEN, false>);
+        const void* fn = p.elem_ok ? reinterpret_cast<const void*>(&convert_elem_kernel<T, WIDEN, true>)
+                                   : reinterpret_cast<const void*>(&convert_elem_kernel<T, WIDEN, false>);
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
-    if (head > count) head = count;
-    const size_t nvec = (count - head) / kLanes16;
-    Split sp{head, nvec, count - head - nvec * kLanes16};
+    Split& sp = p.sp;
     void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail};
     return launch(reinterpret_cast<const void*>(&convert_vec_kernel<T, WIDEN>), grid_for(sp, 64), args, stream, 64);
 }
 
-// convert_typed's placement rule with dst as the 16-bit side: head elements bring dst to a 16-B boundary, and src
-// (fp32, or 16 bits wide like dst) must be on one there too; any other placement takes the element-wise kernel.
+// place_pass with dst as the 16-bit side; src is fp32, or 16 bits wide like dst.
 template <typename T, typename S>
 int convert_scaled_typed(const void* src, void* dst, size_t count, ScalarArg sa, hipStream_t stream) {
     auto s = static_cast<const unsigned char*>(src);
     auto d = static_cast<unsigned char*>(dst);
-    const uintptr_t as = reinterpret_cast<uintptr_t>(src), ad = reinterpret_cast<uintptr_t>(dst);
-    const bool elem_ok = ad % sizeof(T) == 0 && as % sizeof(S) == 0;
-    size_t head = elem_ok ? ((16 - (ad & 15)) & 15) / sizeof(T) : 0;
-    if (!elem_ok || ((as + head * sizeof(S)) & 15)) {
+    PassPlacement p =
+        place_pass(reinterpret_cast<uintptr_t>(dst), sizeof(T), reinterpret_cast<uintptr_t>(src), sizeof(S), count);
+    if (!p.vec_ok) {
         void* args[] = {&s, &d, &count, &sa};
-        const void* fn = elem_ok ? reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, true>)
-                                 : reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, false>);
+        const void* fn = p.elem_ok ? reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, true>)
+                                   : reinterpret_cast<const void*>(&convert_scaled_elem_kernel<T, S, false>);
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
-    if (head > count) head = count;
-    const size_t nvec = (count - head) / kLanes16;
-    Split sp{head, nvec, count - head - nvec * kLanes16};
+    Split& sp = p.sp;
     void* args[] = {&s, &d, &sp.head, &sp.nvec, &sp.tail, &sa};
     return launch(reinterpret_cast<const void*>(&convert_scaled_vec_kernel<T, S>), grid_for(sp, 64), args, stream, 64);
 }

@@ -630,6 +630,107 @@ def test_coalescing_turned_off(gpu, monkeypatch):
                 assert out[r][i].tobytes() == want[i][r].tobytes(), (off, r, i)
 
 
+# A queued call owns its scalar: the op may be destroyed, and its slot taken by another scalar, before group_end.
+FIRST_S, SECOND_S = np.float32(0.5), np.float32(3.0)
+SLOT_N = 1031
+
+
+def _unit_interval_inputs(seed, dt, n):
+    """Inputs in [1, 2): x * 0.5 and x * 3.0 differ for every one of them."""
+    x = np.random.default_rng(seed).uniform(1.0, 2.0, n).astype(np.float32)
+    return x if dt == 7 else (x.view(np.uint32) >> 16).astype(np.uint16)
+
+
+def _create_scaling_op(comm, kind, dt, s):
+    hs = np.array([s], np.float32)  # fp32 is the operands' dtype for the pre-multiplied sum, and the wide scalar's
+    create = comm.red_op_create_premul_sum if kind == "premul" else comm.red_op_create_wide_scaled_sum
+    rc, op = create(hs.ctypes.data, dt, 1)
+    assert rc == 0, rc
+    return op
+
+
+def _assert_differ_everywhere(a, b):
+    assert a.shape == b.shape and np.all(a != b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,dt", [("premul", 7), ("wide_scaled", 9)])
+def test_queued_call_keeps_its_scalar_world1(gpu, kind, dt):
+    """W = 1: an all-reduce queued with a host-immediate scalar of 0.5, then the op destroyed and one with 3.0 created
+    in the same slot, then group_end.  The result is the 0.5 one, bit for bit."""
+    import torch
+    import dccl_amd as d
+    from tests.test_wide_scaled import scaled_sum
+    x = _unit_interval_inputs(61, dt, SLOT_N)
+    if kind == "premul":
+        want, other = scaled(x, dt, FIRST_S), scaled(x, dt, SECOND_S)
+    else:
+        want, other = scaled_sum([x], dt, FIRST_S), scaled_sum([x], dt, SECOND_S)
+    _assert_differ_everywhere(want, other)
+
+    def body(comm, r):
+        stream = torch.cuda.Stream()
+        send = torch.from_numpy(x.view(np.uint8).copy()).cuda()
+        recv = torch.zeros_like(send)
+        torch.cuda.synchronize()
+        op = _create_scaling_op(comm, kind, dt, FIRST_S)
+        assert d.group_start() == 0
+        assert comm.all_reduce(send.data_ptr(), recv.data_ptr(), SLOT_N, dt, op, stream.cuda_stream) == 0
+        assert comm.red_op_destroy(op) == 0
+        again = _create_scaling_op(comm, kind, dt, SECOND_S)
+        assert again == op  # the same slot: whoever still looked there would find 3.0
+        assert d.group_end() == 0
+        stream.synchronize()
+        assert comm.red_op_destroy(again) == 0
+        return recv.cpu().numpy()
+
+    out = run_ranks(1, body)
+    assert out[0].tobytes() == want.tobytes()
+
+
+@pytest.mark.gpu
+def test_packed_run_keeps_its_scalar(gpu, monkeypatch):
+    """W = 2 thread ranks: two small all-reduces with one host-immediate pre-multiplied sum (0.5) make one packed run;
+    the op is destroyed and recreated with 3.0 before group_end.  Both results are the 0.5 ones, bit for bit.  Each
+    tensor has W * 1,031 elements: an all-reduce's count is a multiple of W."""
+    import torch
+    import dccl_amd as d
+    monkeypatch.setenv("DCCL_ALLREDUCE_ALGORITHM", "")
+    monkeypatch.delenv("DCCL_GROUP_COALESCE", raising=False)
+    monkeypatch.delenv("DCCL_GROUP_COALESCE_MAX_BYTES", raising=False)
+    W, n, dt = 2, 2 * SLOT_N, 7
+    inputs = [[_unit_interval_inputs(70 + 2 * r + i, dt, n) for i in range(2)] for r in range(W)]
+    want = [simulate("all_reduce", "", [inputs[r][i] for r in range(W)], dt, SUM, FIRST_S, W) for i in range(2)]
+    other = [simulate("all_reduce", "", [inputs[r][i] for r in range(W)], dt, SUM, SECOND_S, W) for i in range(2)]
+    for i in range(2):
+        for r in range(W):
+            _assert_differ_everywhere(want[i][r], other[i][r])
+
+    def body(comm, r):
+        stream = torch.cuda.Stream()
+        ts = [torch.from_numpy(x.copy()).cuda() for x in inputs[r]]
+        torch.cuda.synchronize()
+        op = _create_scaling_op(comm, "premul", dt, FIRST_S)
+        assert d.group_start() == 0
+        for t in ts:
+            assert comm.all_reduce(t.data_ptr(), t.data_ptr(), n, dt, op, stream.cuda_stream) == 0
+        assert comm.red_op_destroy(op) == 0
+        again = _create_scaling_op(comm, "premul", dt, SECOND_S)
+        assert again == op
+        assert d.group_end() == 0
+        stream.synchronize()
+        assert comm.red_op_destroy(again) == 0
+        return [t.cpu().numpy() for t in ts]
+
+    before = d.group_stats()
+    out = run_ranks(W, body)
+    delta = stats_delta(before)
+    assert delta["coalesced_runs"] == W and delta["tensors_coalesced"] == 2 * W
+    for r in range(W):
+        for i in range(2):
+            assert out[r][i].tobytes() == want[i][r].tobytes(), (r, i)
+
+
 def _ipc_group_rank(r, W, counts, tag, q):
     os.environ["DCCL_BOOTSTRAP_TAG"] = tag
     os.environ.setdefault("DCCL_IPC_TIMEOUT_S", "60")

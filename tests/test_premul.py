@@ -12,15 +12,12 @@ RCCL all-reduce across processes.
 """
 import ctypes
 import fractions
-import multiprocessing as mp
-import os
-import uuid
 
 import numpy as np
 import pytest
 
 import oracle
-from tests import rabsim, ringsim
+from tests import rabsim, ringsim, xproc
 from tests.test_collectives import _expected_allreduce, run_ranks
 from tests.test_direct import chain_expected
 from tests.test_oracle import fp_equal
@@ -555,7 +552,7 @@ def _xp_scalar():
     return to_dtype([0.5], XP_DT)
 
 
-def _xp_all_reduce(comm, r, torch):
+def _xp_all_reduce(comm, r, W, torch):
     s = _xp_scalar()
     rc, op = comm.red_op_create_premul_sum(s.ctypes.data, XP_DT, HOST)
     assert rc == 0, rc
@@ -568,62 +565,6 @@ def _xp_all_reduce(comm, r, torch):
     torch.cuda.synchronize()
     assert comm.red_op_destroy(op) == 0
     return buf.cpu().numpy()
-
-
-def _ipc_premul_rank(r, tag, q):
-    os.environ["DCCL_BOOTSTRAP_TAG"] = tag
-    os.environ.setdefault("DCCL_IPC_TIMEOUT_S", "60")
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        comm = dccl_amd.Comm.ipc(XP_W, r)
-        try:
-            out = _xp_all_reduce(comm, r, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
-def _rccl_premul_rank(r, hostid, conn, algo, q):
-    os.environ.update({"NCCL_HOSTID": f"{hostid}-{r}", "NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1",
-                       "DCCL_ALLREDUCE_ALGORITHM": algo})
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        if r == 0:
-            uid = dccl_amd.Comm.unique_id()
-            conn.send(uid)
-        else:
-            uid = conn.recv()
-        comm = dccl_amd.Comm.rccl(XP_W, r, uid)
-        try:
-            out = _xp_all_reduce(comm, r, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
-def _collect(ps, q):
-    for p in ps:
-        p.start()
-    results = {}
-    try:
-        for _ in range(len(ps)):
-            r, res, err = q.get(timeout=240)
-            assert err is None, (r, err)
-            results[r] = res
-    finally:
-        for p in ps:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    return results
 
 
 def _check_xp(results):
@@ -639,11 +580,7 @@ def _check_xp(results):
 @pytest.mark.gpu
 def test_premul_ipc_processes(gpu):
     """One process per rank on the IPC transport: the fused chain reads the peers' scratch copies."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    tag = "test_" + uuid.uuid4().hex[:12]
-    ps = [ctx.Process(target=_ipc_premul_rank, args=(r, tag, q)) for r in range(XP_W)]
-    _check_xp(_collect(ps, q))
+    _check_xp(xproc.run_ipc(XP_W, _xp_all_reduce))
 
 
 @pytest.mark.gpu
@@ -653,9 +590,4 @@ def test_premul_rccl_processes(gpu, algo):
     import dccl_amd
     if not dccl_amd.lib.dccl_rccl_available():
         pytest.skip("librccl not loadable")
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    a, b = ctx.Pipe()
-    hostid = "dccl-test-" + uuid.uuid4().hex[:10]
-    ps = [ctx.Process(target=_rccl_premul_rank, args=(r, hostid, a if r == 0 else b, algo, q)) for r in range(XP_W)]
-    _check_xp(_collect(ps, q))
+    _check_xp(xproc.run_rccl(XP_W, _xp_all_reduce, algo))

@@ -26,20 +26,18 @@ s = 1 / (nsend + 1) runs as well but nothing relies on it: for a power-of-two di
 unscaled one coincides with the contract.
 """
 import ctypes
-import multiprocessing as mp
 import os
 import subprocess
 import sys
-import uuid
 
 import numpy as np
 import pytest
 
-from tests import rabsim, ringsim
+from tests import rabsim, ringsim, xproc
 from tests.test_collectives import run_ranks
 from tests.test_oracle import fp_equal
 from tests.test_wide_sum import (BF16, CHAIN_CASES, CONVERT_PLACES, DST_OFF, DTS, F16, F32, GUARD_ELEMS, SEED, STRIDE_N,
-                                 SUM, _call, _collect, _copy, _f32_add, _zero_outside, all_patterns, chain_stream,
+                                 SUM, _call, _copy, _f32_add, _zero_outside, all_patterns, chain_stream,
                                  collective_inputs, expected_collective, family_ops, is_nan16, narrow, narrow_inputs,
                                  share_differs, to_bits, tree_acc, wide_acc, wide_sum, widen)
 
@@ -750,45 +748,6 @@ def _xp_all_reduce(comm, r, W, torch):
     return buf.cpu().numpy()
 
 
-def _ipc_scaled_rank(r, W, tag, q):
-    os.environ["DCCL_BOOTSTRAP_TAG"] = tag
-    os.environ.setdefault("DCCL_IPC_TIMEOUT_S", "60")
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        comm = dccl_amd.Comm.ipc(W, r)
-        try:
-            out = _xp_all_reduce(comm, r, W, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
-def _rccl_scaled_rank(r, W, hostid, conn, q):
-    os.environ.update({"NCCL_HOSTID": f"{hostid}-{r}", "NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1",
-                       "DCCL_ALLREDUCE_ALGORITHM": "ring"})
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        if r == 0:
-            uid = dccl_amd.Comm.unique_id()
-            conn.send(uid)
-        else:
-            uid = conn.recv()
-        comm = dccl_amd.Comm.rccl(W, r, uid)
-        try:
-            out = _xp_all_reduce(comm, r, W, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
 def _check_xp(results, W):
     xs = _xp_inputs(W)
     want = expected_scaled_collective("all_reduce", xs, XP_DT, "ring", mean_scalar(W))
@@ -803,11 +762,7 @@ def _check_xp(results, W):
 def test_wide_scaled_ipc_processes(gpu):
     """One process per rank on the IPC transport, W = 3: the fused scaled chain reads the peers' scratch copies."""
     W = 3
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    tag = "test_" + uuid.uuid4().hex[:12]
-    ps = [ctx.Process(target=_ipc_scaled_rank, args=(r, W, tag, q)) for r in range(W)]
-    _check_xp(_collect(ps, q), W)
+    _check_xp(xproc.run_ipc(W, _xp_all_reduce), W)
 
 
 @pytest.mark.gpu
@@ -817,9 +772,4 @@ def test_wide_scaled_rccl_processes(gpu):
     if not dccl_amd.lib.dccl_rccl_available():
         pytest.skip("librccl not loadable")
     W = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    a, b = ctx.Pipe()
-    hostid = "dccl-test-" + uuid.uuid4().hex[:10]
-    ps = [ctx.Process(target=_rccl_scaled_rank, args=(r, W, hostid, a if r == 0 else b, q)) for r in range(W)]
-    _check_xp(_collect(ps, q), W)
+    _check_xp(xproc.run_rccl(W, _xp_all_reduce), W)

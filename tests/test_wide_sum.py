@@ -25,17 +25,15 @@ toss, while on 4096 it is 0.7 points.
               adds in another order cannot pass.
 """
 import ctypes
-import multiprocessing as mp
 import os
 import subprocess
 import sys
-import uuid
 
 import numpy as np
 import pytest
 
 import oracle
-from tests import rabsim, ringsim
+from tests import rabsim, ringsim, xproc
 from tests.test_collectives import _expected_allreduce, run_ranks
 from tests.test_direct import chain_expected
 from tests.test_oracle import fp_equal
@@ -722,62 +720,6 @@ def _xp_all_reduce(comm, r, W, torch):
     return buf.cpu().numpy()
 
 
-def _ipc_wide_rank(r, W, tag, q):
-    os.environ["DCCL_BOOTSTRAP_TAG"] = tag
-    os.environ.setdefault("DCCL_IPC_TIMEOUT_S", "60")
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        comm = dccl_amd.Comm.ipc(W, r)
-        try:
-            out = _xp_all_reduce(comm, r, W, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
-def _rccl_wide_rank(r, W, hostid, conn, q):
-    os.environ.update({"NCCL_HOSTID": f"{hostid}-{r}", "NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1",
-                       "DCCL_ALLREDUCE_ALGORITHM": "ring"})
-    try:
-        import torch
-        import dccl_amd
-        torch.cuda.set_device(0)
-        if r == 0:
-            uid = dccl_amd.Comm.unique_id()
-            conn.send(uid)
-        else:
-            uid = conn.recv()
-        comm = dccl_amd.Comm.rccl(W, r, uid)
-        try:
-            out = _xp_all_reduce(comm, r, W, torch)
-        finally:
-            fin = comm.finalize()
-        q.put((r, (out, fin), None))
-    except Exception as e:  # pragma: no cover - reported by the parent
-        q.put((r, None, repr(e)))
-
-
-def _collect(ps, q):
-    for p in ps:
-        p.start()
-    results = {}
-    try:
-        for _ in range(len(ps)):
-            r, res, err = q.get(timeout=240)
-            assert err is None, (r, err)
-            results[r] = res
-    finally:
-        for p in ps:
-            p.join(timeout=60)
-            if p.is_alive():
-                p.kill()
-    return results
-
-
 def _check_xp(results, W):
     want = expected_collective("all_reduce", _xp_inputs(W), XP_DT, "ring")
     for r in range(W):
@@ -790,11 +732,7 @@ def _check_xp(results, W):
 def test_wide_ipc_processes(gpu):
     """One process per rank on the IPC transport, W = 3: the fused wide chain reads the peers' scratch copies."""
     W = 3
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    tag = "test_" + uuid.uuid4().hex[:12]
-    ps = [ctx.Process(target=_ipc_wide_rank, args=(r, W, tag, q)) for r in range(W)]
-    _check_xp(_collect(ps, q), W)
+    _check_xp(xproc.run_ipc(W, _xp_all_reduce), W)
 
 
 @pytest.mark.gpu
@@ -804,9 +742,4 @@ def test_wide_rccl_processes(gpu):
     if not dccl_amd.lib.dccl_rccl_available():
         pytest.skip("librccl not loadable")
     W = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    a, b = ctx.Pipe()
-    hostid = "dccl-test-" + uuid.uuid4().hex[:10]
-    ps = [ctx.Process(target=_rccl_wide_rank, args=(r, W, hostid, a if r == 0 else b, q)) for r in range(W)]
-    _check_xp(_collect(ps, q), W)
+    _check_xp(xproc.run_rccl(W, _xp_all_reduce), W)
