@@ -11,40 +11,23 @@
 
 namespace dccl_amd {
 
-struct ChainPlacement {
-    SendList sl;
-    bool elem_ok;   // every operand element-aligned
-    bool in_phase;  // every operand in the destination's 16-B phase
-};
-
-template <typename T>
-ChainPlacement classify_chain(const void* const* sends, int nsend, const void* own, const void* dst) {
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst), ao = reinterpret_cast<uintptr_t>(own);
-    ChainPlacement c{{}, ad % sizeof(T) == 0 && ao % sizeof(T) == 0, ((ad ^ ao) & 15) == 0};
-    for (int k = 0; k < nsend; ++k) {
-        c.sl.p[k] = static_cast<const unsigned char*>(sends[k]);
-        const uintptr_t a = reinterpret_cast<uintptr_t>(sends[k]);
-        if (a % sizeof(T)) c.elem_ok = false;
-        if ((a ^ ad) & 15) c.in_phase = false;
-    }
-    return c;
-}
-
 // KN names the kernels: KN::template vec<T, K>() and KN::template elem<T, ALIGNED>() give their addresses;
-// `extra` is what they take after the chain's own arguments (the pre-multiplied chain's scalar).
+// `extra` is what they take after the chain's own arguments (the pre-multiplied chain's scalar).  Where the
+// operands lie: classify (routing.hpp), the plain chain's classifier.
 template <typename KN, typename T, typename... Extra>
 int launch_chain_form(const void* const* sends, int nsend, const void* own, void* dst, size_t count,
                       hipStream_t stream, Extra... extra) {
-    ChainPlacement c = classify_chain<T>(sends, nsend, own, dst);
+    const Placement c = classify(sends, nsend, own, dst, sizeof(T));
+    SendList sl = send_list(sends, nsend);
     auto o = static_cast<const unsigned char*>(own);
     auto d = static_cast<unsigned char*>(dst);
-    if (!c.elem_ok || !c.in_phase) {
-        void* args[] = {&c.sl, &nsend, &o, &d, &count, &extra...};
+    if (!c.elem_ok || !c.in_phase()) {
+        void* args[] = {&sl, &nsend, &o, &d, &count, &extra...};
         const void* fn = c.elem_ok ? KN::template elem<T, true>() : KN::template elem<T, false>();
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
     Split sp = split_for_vectors<T>(reinterpret_cast<uintptr_t>(dst), count, kDstAlign);
-    void* args[] = {&c.sl, &o, &d, &sp.head, &sp.nvec, &sp.tail, &extra...};
+    void* args[] = {&sl, &o, &d, &sp.head, &sp.nvec, &sp.tail, &extra...};
     return with_k<1, 8>(nsend, [&](auto K) {
         return launch(KN::template vec<T, K.value>(), grid_for(sp, DefaultCfg::TILE), args, stream, DefaultCfg::BLOCK,
                       caps::lds(caps::kChain, K.value, caps_bytes(sp.nvec * 16)));

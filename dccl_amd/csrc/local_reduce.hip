@@ -81,82 +81,20 @@ int reduce_typed(const void* send, void* recv, size_t count, hipStream_t stream,
         const Split sp = split_for_vectors<T>(ar, count, align);
         const uintptr_t a = (as + sp.head * sizeof(T)) & ~uintptr_t(15);
         return (a & 127) ? launch_shift<T, OP, ShiftStraddlePolicy, false, 0, false, kShiftRun>(s, r, count, stream,
-                                                                                                align, 0, grid_cap)
-                         : launch_shift<T, OP, ShiftPolicy, false, 0, false, kShiftRun>(s, r, count, stream, align, 0,
+                                                                                                align, grid_cap)
+                         : launch_shift<T, OP, ShiftPolicy, false, 0, false, kShiftRun>(s, r, count, stream, align,
                                                                                        grid_cap);
     }
     const Split sp = split_for_vectors<T>(ar, count, align);
     if ((as ^ ar) & 15) {
         const uintptr_t a = (as + sp.head * sizeof(T)) & ~uintptr_t(15);  // the shifted kernel's send vectors
         return (a & 127) ? launch_shift<T, OP, ShiftStraddlePolicy, false, 0, true, kShiftRun>(s, r, count, stream,
-                                                                                               align, 0, grid_cap)
-                         : launch_shift<T, OP, ShiftPolicy, false, 0, true, kShiftRun>(s, r, count, stream, align, 0,
+                                                                                               align, grid_cap)
+                         : launch_shift<T, OP, ShiftPolicy, false, 0, true, kShiftRun>(s, r, count, stream, align,
                                                                                       grid_cap);
     }
     if ((as ^ ar) & 127) return launch_vec<T, OP, StraddleCfg>(s, r, sp, stream, grid_cap);
     return launch_vec<T, OP, DefaultCfg>(s, r, sp, stream, grid_cap);
-}
-
-// k-way combine: every resident wave keeps k+1 16-B loads per lane in flight, so the resident waves
-// per CU are capped (through unused dynamic LDS, 160 KiB per CU) to keep roughly 50-80 KiB of reads
-// outstanding per CU.  Measured optimum per k at 1 GiB per operand on MI355X, fp32 Sum
-// (tune_multi.py@4f20423, profiles/r1_tune_multi_waves.json): 4-7 % faster than 32 waves for k >= 2.
-// In-phase sources off recv's 128-B line grid (recv is line-aligned past the head): their loads go
-// through the caches, so the line two neighbouring tiles share is fetched once (StraddleCfg's rule).
-// 1 GiB-class A/B on one MI355X (profiles/r1_s5_kway_straddle_ab.json): k = 1 76.7 -> 85.6 %,
-// k = 2 75.5 -> 78.0 %, k = 4 74.4 -> 78.4 %, k = 7 72.3 -> 77.5 % of HBM peak.
-inline bool any_straddles(const SendList& sl, int nsend, size_t off) {
-    for (int k = 0; k < nsend; ++k)
-        if ((reinterpret_cast<uintptr_t>(sl.p[k]) + off) & 127) return true;
-    return false;
-}
-
-template <typename T, int OP, int K>
-int launch_multi_vec(SendList sl, unsigned char* r, Split sp, hipStream_t stream) {
-    using C = DefaultCfg;
-    const size_t grid = grid_for(sp, C::TILE);
-    void* args[] = {&sl, &r, &sp.head, &sp.nvec, &sp.tail};
-    return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
-                  caps::lds(caps::kMulti, K, caps_bytes(sp.nvec * 16)));
-}
-
-template <typename T, int OP>
-int reduce_multi_typed(const void* const* sends, int nsend, void* recv, size_t count, hipStream_t stream) {
-    // One source is the pairwise combine itself: take its tuned dispatch (every alignment class).  The
-    // k-way kernel at k = 1 ran at 78.7 % of peak at 1 GiB against 85 % for the pairwise kernel
-    // (profiles/r2_kway_pmc.json, traffic exactly 3N in both).
-    if (nsend == 1) return reduce_typed<T, OP>(sends[0], recv, count, stream);
-    SendList sl{};
-    const uintptr_t ar = reinterpret_cast<uintptr_t>(recv);
-    bool vec_ok = (ar % sizeof(T)) == 0;
-    for (int k = 0; k < nsend; ++k) {
-        sl.p[k] = static_cast<const unsigned char*>(sends[k]);
-        if ((reinterpret_cast<uintptr_t>(sends[k]) ^ ar) & 15) vec_ok = false;
-    }
-    auto r = static_cast<unsigned char*>(recv);
-    if (ar % sizeof(T)) {  // recv not element-aligned: 16-B accesses at its own address, sources at any phase
-        if constexpr (sizeof(T) > 1) {
-            PhaseList ph{};
-            for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
-            return multi_unaligned_typed<T, OP>(sl, ph, nsend, r, count, stream);
-        }
-    }
-    if (!vec_ok) {  // an element-aligned recv and sources at other 16-B (or byte) phases: the phased kernel
-        if constexpr (sizeof(T) > 1) {
-            if (caps::phased_via_windows(false, nsend, caps_bytes(count * sizeof(T)), (ar & 15) == 0)) {  // or the windows kernel (caps.hpp)
-                PhaseList ph{};
-                for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
-                return multi_unaligned_typed<T, OP>(sl, ph, nsend, r, count, stream);
-            }
-        }
-        const Split sp = split_for_vectors<T>(ar, count, recv_align());
-        PhaseList ph{};
-        for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], sp.head * sizeof(T));
-        return multi_phased_typed<T, OP>(sl, ph, nsend, r, sp, stream);
-    }
-    const Split sp = split_for_vectors<T>(ar, count, recv_align());
-    if (any_straddles(sl, nsend, sp.head * sizeof(T))) return multi_straddle_typed<T, OP>(sl, nsend, r, sp, stream);
-    return with_k<2, 8>(nsend, [&](auto K) { return launch_multi_vec<T, OP, K.value>(sl, r, sp, stream); });
 }
 
 // ---------------------------------------------------------------------------------
@@ -192,70 +130,61 @@ __global__ __launch_bounds__(64) void copy_multi_kernel(CopyList cl, int npairs,
     }
 }
 
-template <typename T, int OP, int K>
-int launch_chain_vec(SendList sl, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream,
-                     size_t grid_cap) {
+// k-way and chain combines: every resident wave keeps k+1 16-B loads per lane in flight, so the resident waves
+// per CU are capped (through unused dynamic LDS, 160 KiB per CU) to keep roughly 50-80 KiB of reads
+// outstanding per CU.  Measured optimum per k at 1 GiB per operand on MI355X, fp32 Sum
+// (tune_multi.py@4f20423, profiles/r1_tune_multi_waves.json): 4-7 % faster than 32 waves for k >= 2.
+template <typename T, int OP, int K, bool CHAIN>
+int launch_in_phase(SendList sl, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream,
+                    size_t grid_cap) {
     using C = DefaultCfg;
     size_t grid = grid_for(sp, C::TILE);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
-    void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
-    return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
-                  caps::lds(caps::kChain, K, caps_bytes(sp.nvec * 16)));
+    const size_t lds = caps::lds(CHAIN ? caps::kChain : caps::kMulti, K, caps_bytes(sp.nvec * 16));
+    if constexpr (CHAIN) {
+        void* args[] = {&sl, &own, &d, &sp.head, &sp.nvec, &sp.tail};
+        return launch(reinterpret_cast<const void*>(&reduce_chain_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
+                      lds);
+    } else {
+        void* args[] = {&sl, &d, &sp.head, &sp.nvec, &sp.tail};
+        return launch(reinterpret_cast<const void*>(&reduce_multi_vec_kernel<T, OP, K, C>), grid, args, stream, C::BLOCK,
+                      lds);
+    }
 }
 
-// grid_cap: as reduce_typed's, for the zero-copy host chain combine; it applies to the in-phase launches (the host
-// staging keeps every operand 256-B aligned), the other alignment classes keep their own grids.
-template <typename T, int OP>
-int reduce_chain_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count,
-                       hipStream_t stream, size_t grid_cap) {
-    // dst = op(own, s0) in place is the pairwise combine recv = op(recv, send) with recv = own = dst
-    if (nsend == 1 && own == dst) return reduce_typed<T, OP>(sends[0], dst, count, stream, grid_cap);
-    SendList sl{};
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst), ao = reinterpret_cast<uintptr_t>(own);
-    bool src_off = false;  // some source at another 16-B phase than dst
-    for (int k = 0; k < nsend; ++k) {
-        sl.p[k] = static_cast<const unsigned char*>(sends[k]);
-        if ((reinterpret_cast<uintptr_t>(sends[k]) ^ ad) & 15) src_off = true;
-    }
-    const bool vec_ok = (ad % sizeof(T)) == 0 && ((ad ^ ao) & 15) == 0 && !src_off;
+// The k-way (CHAIN false: own = dst = recv) and chain combines: route() (routing.hpp) says where the operands lie,
+// this switch launches.  grid_cap: as reduce_typed's, for the zero-copy host chain combine; only the chain takes
+// it, and it applies to the in-phase launches (the host staging keeps every operand 256-B aligned), the other
+// alignment classes keep their own grids.
+template <typename T, int OP, bool CHAIN>
+int reduce_many_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count,
+                      hipStream_t stream, size_t grid_cap) {
+    if constexpr (!CHAIN) grid_cap = 0;
+    const Routed rt = route(CHAIN, nsend, sizeof(T), sends, own, dst, count, recv_align(), caps_bytes(count * sizeof(T)));
+    const SendList sl = send_list(sends, nsend);
     const auto o = static_cast<const unsigned char*>(own);
-    auto d = static_cast<unsigned char*>(dst);
-    if (ad % sizeof(T)) {  // dst not element-aligned: 16-B accesses at its own address, operands at any phase
-        if constexpr (sizeof(T) > 1) {
-            PhaseList ph{};
-            for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
-            ph.p[nsend] = phase_word(o, 0);
-            return chain_unaligned_typed<T, OP>(sl, ph, nsend, o, d, count, stream);
-        }
+    const auto d = static_cast<unsigned char*>(dst);
+    switch (rt.route) {
+    case kRoutePair: return reduce_typed<T, OP>(sends[0], dst, count, stream, grid_cap);
+    case kRouteWindowsDstOff:
+    case kRouteWindowsViaCaps:
+        if constexpr (sizeof(T) > 1) return unaligned_typed<T, OP, CHAIN>(sl, rt.ph, nsend, o, d, count, stream);
+        break;  // a one-byte element is always aligned and route() keeps it on the phased kernels
+    case kRoutePhased: return phased_typed<T, OP, CHAIN>(sl, rt.ph, nsend, o, d, rt.sp, stream);
+    case kRouteStraddle: return straddle_typed<T, OP, CHAIN>(sl, nsend, o, d, rt.sp, stream);
+    case kRouteInPhase:
+        return with_k<(CHAIN ? 1 : 2), 8>(nsend, [&](auto K) {
+            return launch_in_phase<T, OP, K.value, CHAIN>(sl, o, d, rt.sp, stream, grid_cap);
+        });
     }
-    if (!vec_ok) {  // an element-aligned dst and operands at other 16-B (or byte) phases: the phased kernel
-        if constexpr (sizeof(T) > 1) {
-            // or the windows kernel (caps.hpp), whose off-phase forms were measured with sources off phase (not
-            // with `own` alone off phase: that launch keeps the phased kernels)
-            if (src_off && caps::phased_via_windows(true, nsend, caps_bytes(count * sizeof(T)), (ad & 15) == 0)) {
-                PhaseList ph{};
-                for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], 0);
-                ph.p[nsend] = phase_word(o, 0);
-                return chain_unaligned_typed<T, OP>(sl, ph, nsend, o, d, count, stream);
-            }
-        }
-        const Split sp = split_for_vectors<T>(ad, count, recv_align());
-        PhaseList ph{};
-        for (int k = 0; k < nsend; ++k) ph.p[k] = phase_word(sl.p[k], sp.head * sizeof(T));
-        ph.p[nsend] = phase_word(o, sp.head * sizeof(T));
-        return chain_phased_typed<T, OP>(sl, ph, nsend, o, d, sp, stream);
-    }
-    const Split sp = split_for_vectors<T>(ad, count, recv_align());
-    if (any_straddles(sl, nsend, sp.head * sizeof(T))) return chain_straddle_typed<T, OP>(sl, nsend, o, d, sp, stream);
-    return with_k<1, 8>(nsend,
-                        [&](auto K) { return launch_chain_vec<T, OP, K.value>(sl, o, d, sp, stream, grid_cap); });
+    return DCCL_INTERNAL_ERROR;
 }
 
 struct ReduceChainFn {
     template <typename T, int OP>
     static int run(const void* const* sends, int nsend, const void* own, void* dst, size_t count, hipStream_t stream,
                    size_t grid_cap) {
-        return reduce_chain_typed<T, OP>(sends, nsend, own, dst, count, stream, grid_cap);
+        return reduce_many_typed<T, OP, true>(sends, nsend, own, dst, count, stream, grid_cap);
     }
 };
 
@@ -269,7 +198,7 @@ struct ReduceFn {
 struct ReduceMultiFn {
     template <typename T, int OP>
     static int run(const void* const* sends, int nsend, void* recv, size_t count, hipStream_t stream) {
-        return reduce_multi_typed<T, OP>(sends, nsend, recv, count, stream);
+        return reduce_many_typed<T, OP, false>(sends, nsend, recv, recv, count, stream, 0);
     }
 };
 

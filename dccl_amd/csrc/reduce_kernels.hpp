@@ -1,5 +1,11 @@
-// dccl_amd/csrc/reduce_kernels.hpp — device code of the combine and its launch helpers, shared by
-// the production entry points (local_reduce.hip) and the tuning variants (tune_kernels.hip).
+// dccl_amd/csrc/reduce_kernels.hpp — device code of the combine and its launch helpers, shared by the
+// translation units that instantiate it: local_reduce.hip (pairwise, in-phase k-way / chain, copy), phased_multi.hip
+// and phased_chain.hip (operands at other 16-B phases, line-straddling sources), unaligned_multi.hip (a destination
+// off element alignment), premul.hip and wide.hip (the extended chains, through chain_vec_body), copy_rows.hip.
+// Stated once here: the shifted load (ld_phased_issue / ld_phased_finish, funnel_by) and the two association orders
+// (fold_ordered: fold16 over 16-B vectors, fold_elem over single elements).  The kernels that keep a statement of
+// their own say why where they stand (a measured loss, or device code that is pinned).  Where the operands lie and
+// which launch takes them is host-only code: routing.hpp.
 // See local_reduce.hip for the design; SURVEY.md §7 / DESIGN.md §3 for the rooflines.
 #pragma once
 
@@ -13,6 +19,7 @@
 #include "caps.hpp"
 #include "combine.hpp"
 #include "dccl/dccl_reduce.h"
+#include "routing.hpp"
 #include "tile_maps.hpp"
 
 namespace dccl_amd {
@@ -48,8 +55,8 @@ __device__ __forceinline__ void st_elem(unsigned char* base, size_t i, T v) {
 
 // Vector kernel: [head scalars | nvec 16-B vectors | tail scalars], the head aligning recv to its 128-B lines.
 // Shape: BLOCK threads, UNROLL 16-B vectors per thread per operand, cache POLICY bits, XCD (each XCD's blocks walk
-// one contiguous range) or the tile-run order RUN; TAG keeps the production (0) and tuning (1) translation units'
-// instantiations distinct.
+// one contiguous range) or the tile-run order RUN; TAG is always 0 (it stays because the profile tools match the
+// kernels by their full template argument lists).
 template <int BLOCK_, int UNROLL_, int POLICY_, bool XCD_, int TAG = 0, int RUN_ = 1>
 struct VecCfg {
     static constexpr int BLOCK = BLOCK_, UNROLL = UNROLL_, POLICY = POLICY_, RUN = RUN_;  // RUN: run_tile below
@@ -134,8 +141,8 @@ __global__ __launch_bounds__(C::BLOCK) void reduce_vec_kernel(const unsigned cha
 // wave shift; lane 63 loads it itself) and funnel-shifts the 32 bytes by p (v_alignbyte_b32), so every access
 // stays a 16-B vector.  A[nvec] is read although only its first p bytes are send's: an aligned 16-B load never
 // leaves the page of its first byte.  p may be any byte count: a send that is not element-aligned takes this
-// kernel too (SEND_ALIGNED false: its head / tail elements are read bytewise).
-constexpr int kNtExtra = 8;  // policy bit: non-temporal load of lane 63's extra vector
+// kernel too (SEND_ALIGNED false: its head / tail elements are read bytewise).  Lane 63's extra vector is always
+// loaded through the caches.
 
 template <int Q>
 __device__ __forceinline__ u32x4 funnel16(u32x4 lo, u32x4 hi, unsigned b) {
@@ -165,32 +172,66 @@ __device__ __forceinline__ u32x4 dpp16(u32x4 x, u32x4 old) {
 // misaligned_2pass.hpp@4f20423)
 __device__ __forceinline__ u32x4 from_next_lane_or(u32x4 x, u32x4 last) { return dpp16<0x130>(x, last); }
 
+// The 16 bytes that start p bytes (0 < p < 16) into the 32 bytes lo | hi.
+__device__ __forceinline__ u32x4 funnel_by(u32x4 lo, u32x4 hi, unsigned p) {
+    const unsigned b = p & 3;
+    switch (p >> 2) {  // uniform
+    case 0: return funnel16<0>(lo, hi, b);
+    case 1: return funnel16<1>(lo, hi, b);
+    case 2: return funnel16<2>(lo, hi, b);
+    default: return funnel16<3>(lo, hi, b);
+    }
+}
+
+// The shifted load, stated once, in two halves, so a kernel can issue every operand's loads before it uses any of
+// them (one wait for all of them instead of one round trip per operand).  An operand's body starts p bytes
+// (0 <= p < 16, uniform) past the 16-B aligned vector a[0]; vector v of the body (zero for v >= nvec) is
+//   ld_phased_issue: every lane's aligned load a[v] (non-temporal unless !NT) and lane 63's extra vector a[v + 1]
+//                    (through the caches: it is the next tile's first); with p == 0 a[v] is the body's vector
+//                    itself and neither a[nvec] nor the extra vector is read.  One load path for every phase (no
+//                    uniform branch between two operands' loads).
+//   ld_phased_finish: the lane exchange and the funnel shift by p.
+// All 64 lanes call both.  FULL: v and v + 1 lie inside the body (no bounds checks).
+struct PhasedLoad {
+    u32x4 lo, ex;
+};
+__device__ __forceinline__ const u32x4* aligned_base(const unsigned char* body, unsigned p) {
+    return reinterpret_cast<const u32x4*>(body - p);
+}
+template <bool FULL = false, bool NT = true>
+__device__ __forceinline__ PhasedLoad ld_phased_issue(const u32x4* a, unsigned p, size_t v, size_t nvec) {
+    PhasedLoad x{{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    if (FULL || (p != 0 ? v <= nvec : v < nvec)) x.lo = ld16<NT>(a + v);  // a[nvec]: the last p body bytes
+    if (p != 0 && (threadIdx.x & 63) == 63 && (FULL || v < nvec)) x.ex = a[v + 1];
+    return x;
+}
+__device__ __forceinline__ u32x4 ld_phased_finish(const PhasedLoad& x, unsigned p) {
+    if (p == 0) return x.lo;
+    return funnel_by(x.lo, from_next_lane_or(x.lo, x.ex), p);
+}
+// ld_phased: from the operand's body.  The uniform branch on p comes first here, so an operand in phase costs a
+// plain vector load and nothing else (the per-operand kernels and the copies were tuned in this shape).
+__device__ __forceinline__ u32x4 ld_phased(const unsigned char* body, unsigned p, size_t v, size_t nvec) {
+    if (p == 0) return ld_phased_issue(reinterpret_cast<const u32x4*>(body), 0, v, nvec).lo;
+    return ld_phased_finish(ld_phased_issue(aligned_base(body, p), p, v, nvec), p);
+}
+
 template <typename T, int OP, int POLICY, bool XCD, int TAG = 0, bool SEND_ALIGNED = true, int RUN = 1>
 __global__ __launch_bounds__(64) void reduce_shift_kernel(const unsigned char* __restrict__ send,
                                                           unsigned char* __restrict__ recv, size_t head,
                                                           size_t nvec, size_t tail, unsigned p) {
-    const unsigned char* sa = send + head * sizeof(T);
-    const u32x4* va = reinterpret_cast<const u32x4*>(sa - p);  // A: 16-B aligned
+    const u32x4* va = aligned_base(send + head * sizeof(T), p);
     u32x4* vr = reinterpret_cast<u32x4*>(recv + head * sizeof(T));
     const size_t ntiles = (nvec + 63) / 64;
     const size_t bid = XCD ? xcd_remap(blockIdx.x, gridDim.x) : run_tile<RUN>(blockIdx.x, gridDim.x);
-    const unsigned q = p >> 2, b = p & 3;
-    const bool last_lane = threadIdx.x == 63;
     for (size_t t = bid; t < ntiles; t += gridDim.x) {  // uniform per wave: every lane reaches the lane exchange
         const size_t v = t * 64 + threadIdx.x;
-        u32x4 lo = {0u, 0u, 0u, 0u}, ex = {0u, 0u, 0u, 0u}, r = {0u, 0u, 0u, 0u};
-        if (v <= nvec) lo = ld16<(POLICY & kNtSend) != 0>(va + v);
+        __builtin_assume(p != 0);  // a whole vector (nvec > 0) means recv reached its 16-B boundary, send did not
+        u32x4 r = {0u, 0u, 0u, 0u};
+        const PhasedLoad x = ld_phased_issue<false, (POLICY & kNtSend) != 0>(va, p, v, nvec);
         if (v < nvec) r = ld16<(POLICY & kNtRecv) != 0>(vr + v);
-        if (last_lane && v < nvec) ex = ld16<(POLICY & kNtExtra) != 0>(va + v + 1);
-        const u32x4 hi = from_next_lane_or(lo, ex);
+        const u32x4 s = ld_phased_finish(x, p);
         if (v < nvec) {
-            u32x4 s;
-            switch (q) {  // uniform
-            case 0: s = funnel16<0>(lo, hi, b); break;
-            case 1: s = funnel16<1>(lo, hi, b); break;
-            case 2: s = funnel16<2>(lo, hi, b); break;
-            default: s = funnel16<3>(lo, hi, b); break;
-            }
             const u32x4 o = combine16<T, OP>(r, s);
             if constexpr ((POLICY & kNtStore) != 0) __builtin_nontemporal_store(o, vr + v);
             else vr[v] = o;
@@ -200,25 +241,50 @@ __global__ __launch_bounds__(64) void reduce_shift_kernel(const unsigned char* _
 }
 
 // ---------------------------------------------------------------------------------
-// A recv that is not element-aligned (e.g. fp32 at an odd byte address; the reference's host loop takes
-// it with a warning, internal_common.hpp:504-512, its CUDA kernel not at all).  gfx950 executes
-// global_store_dwordx4 at any byte address (unaligned_probe.hip@4f20423 checks every element), so lane i owns
-// the 16 bytes of elements [V i, V i + V) at their displaced address (V = 16 / sizeof(T)): adjacent lanes'
-// windows are disjoint and hold whole elements, so no byte is written twice.  Both operands' windows are
-// read the shifted kernel's way (aligned loads, lane exchange, funnel shift by the operand's own phase);
-// unaligned 16-B loads of recv ran 2-5 points slower, of send 7-10.  A 1 KiB tile spans 9 lines of recv,
-// one shared with the next tile: the launch takes the group-interleaved tile order (tile_order), so 7 of 8 such
-// lines meet in one L2 while the chip sweeps one front, uncapped: 85.1-85.2 % of peak, the aligned kernel's
-// rate, against 80.7-82.1 % for round 2's XCD ranges under a 24-wave cap (profiles/r3_s4_*).  The tail
-// (< V elements) is block 0's, element by element.  Kernel: after ld_phased below.
-// ---------------------------------------------------------------------------------
-typedef u32x4 u32x4_u __attribute__((aligned(1)));
-
-// ---------------------------------------------------------------------------------
 // k-way vector kernel: recv = op(...op(op(recv, s0), s1)..., s{K-1}), one pass.
 // ---------------------------------------------------------------------------------
-struct SendList { const unsigned char* p[8]; };
+// The two association orders of K sources and one more operand, stated once.  w(k) yields operand k: the sources
+// are 0..K-1; operand K is the destination's own data (k-way) or `own` (chain).  Each w(k) is evaluated once, in
+// the order of use, so a caller whose w(k) loads keeps its loads in that order.
+//   k-way: recv = op(...op(op(recv, s0), s1)..., s{K-1})
+//   chain: dst  = op(own, op(s{K-1}, ... op(s2, op(s1, s0))))    (the ring's order)
+template <int K, bool CHAIN, typename W, typename F>
+__device__ __forceinline__ auto fold_ordered(W&& w, F&& op) {
+    if constexpr (CHAIN) {
+        auto acc = w(0);
+#pragma unroll
+        for (int k = 1; k <= K; ++k) acc = op(w(k), acc);
+        return acc;
+    } else {
+        auto acc = w(K);
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc = op(acc, w(k));
+        return acc;
+    }
+}
+// ... over 16-B vectors: w(k) yields operand k's, or they stand loaded in w[0..K],
+template <typename T, int OP, int K, bool CHAIN, typename W>
+__device__ __forceinline__ u32x4 fold16_of(W&& w) {
+    return fold_ordered<K, CHAIN>(w, [](u32x4 a, u32x4 b) { return combine16<T, OP>(a, b); });
+}
+template <typename T, int OP, int K, bool CHAIN>
+__device__ __forceinline__ u32x4 fold16(const u32x4 (&w)[K + 1]) {
+    return fold16_of<T, OP, K, CHAIN>([&](int k) { return w[k]; });
+}
+// ... and for element i, loaded and stored here.  SRC_ALIGNED: the sources (and the chain's own) are
+// element-aligned; DST_ALIGNED: the destination (the k-way's own data) is.
+template <typename T, int OP, int K, bool CHAIN, bool SRC_ALIGNED, bool DST_ALIGNED>
+__device__ __forceinline__ void fold_elem(const unsigned char* const (&src)[8], const unsigned char* own,
+                                          unsigned char* dst, size_t i) {
+    const T acc = fold_ordered<K, CHAIN>(
+        [&](int k) { return k < K ? ld_elem<T, SRC_ALIGNED>(src[k], i) : ld_elem<T, CHAIN ? SRC_ALIGNED : DST_ALIGNED>(own, i); },
+        [](T a, T b) { return Combine<T, OP>::apply(a, b); });
+    st_elem<T, DST_ALIGNED>(dst, i, acc);
+}
 
+// SendList (routing.hpp): the sources' addresses, a plain struct kernel argument.
+// This kernel spells the k-way order out itself, in both loops: its device code is pinned, and every
+// form of it through fold16 / fold_elem changed the code (commuted operands, another scalar schedule).
 template <typename T, int OP, int K, typename C>
 __global__ __launch_bounds__(C::BLOCK) void reduce_multi_vec_kernel(SendList sends, unsigned char* __restrict__ recv,
                                                                     size_t head, size_t nvec, size_t tail) {
@@ -355,34 +421,6 @@ __global__ __launch_bounds__(C::BLOCK) void reduce_chain_vec_kernel(SendList sen
 // every operand's loads first under caps of their own (below; DESIGN.md §3, caps.hpp).
 // One-wave blocks and a per-tile loop uniform per wave: every lane reaches the lane exchange.
 // ---------------------------------------------------------------------------------
-struct PhaseList { unsigned p[9]; };
-
-// ld_phased in two halves, so a kernel can issue every operand's loads before it uses any of them (one wait
-// for all of them instead of one round trip per operand): ld_phased_issue starts the loads,
-// ld_phased_finish does the lane exchange and the shift.  All 64 lanes call both (p is uniform).
-struct PhasedLoad {
-    u32x4 lo, ex;
-};
-__device__ __forceinline__ PhasedLoad ld_phased_issue(const unsigned char* body, unsigned p, size_t v, size_t nvec) {
-    // one load path for every phase (no uniform branch between two operands' loads): with p == 0, va is
-    // the body itself and vector nvec is not read
-    PhasedLoad x{{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-    const u32x4* va = reinterpret_cast<const u32x4*>(body - p);
-    if (p != 0 ? v <= nvec : v < nvec) x.lo = __builtin_nontemporal_load(va + v);  // A[nvec]: the last p bytes
-    if (p != 0 && (threadIdx.x & 63) == 63 && v < nvec) x.ex = va[v + 1];
-    return x;
-}
-__device__ __forceinline__ u32x4 ld_phased_finish(const PhasedLoad& x, unsigned p) {
-    if (p == 0) return x.lo;
-    const u32x4 hi = from_next_lane_or(x.lo, x.ex);
-    const unsigned b = p & 3;
-    switch (p >> 2) {  // uniform
-    case 0: return funnel16<0>(x.lo, hi, b);
-    case 1: return funnel16<1>(x.lo, hi, b);
-    case 2: return funnel16<2>(x.lo, hi, b);
-    default: return funnel16<3>(x.lo, hi, b);
-    }
-}
 
 // XCD: consecutive tiles on one XCD (xcd_remap), so the vector lane 63 reads past its tile and the
 // next tile's first line meet in one L2.  It pays while few operands share the L2.  1 GiB fp32 Sum,
@@ -394,53 +432,9 @@ inline constexpr int kPhasedXcdMaxK = 4;
 // loads-first form (ld_phased_issue / ld_phased_finish) under that cap and in the tile-run order caps::kRun
 // (caps.hpp); uncapped it loses (too many streams in flight).
 
-// The 16 body bytes of vector v (zero for v >= nvec) of an operand whose body starts at `body`,
-// phase p.  All 64 lanes must call it (p is uniform).
-__device__ __forceinline__ u32x4 ld_phased(const unsigned char* body, unsigned p, size_t v, size_t nvec) {
-    u32x4 lo = {0u, 0u, 0u, 0u};
-    if (p == 0) {
-        if (v < nvec) lo = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(body) + v);
-        return lo;
-    }
-    const u32x4* va = reinterpret_cast<const u32x4*>(body - p);
-    const bool last_lane = (threadIdx.x & 63) == 63;
-    u32x4 ex = {0u, 0u, 0u, 0u};
-    if (v <= nvec) lo = __builtin_nontemporal_load(va + v);  // A[nvec] holds the last p body bytes
-    if (last_lane && v < nvec) ex = va[v + 1];
-    const u32x4 hi = from_next_lane_or(lo, ex);
-    const unsigned b = p & 3;
-    switch (p >> 2) {  // uniform
-    case 0: return funnel16<0>(lo, hi, b);
-    case 1: return funnel16<1>(lo, hi, b);
-    case 2: return funnel16<2>(lo, hi, b);
-    default: return funnel16<3>(lo, hi, b);
-    }
-}
-
-// grid: a multiple of 8.  Block b takes tile (b % 8) * (grid / 8) + b / 8, then strides by grid.  Lane i's
-// window is recv's elements [V i, V i + V): its 16 bytes at the displaced address are read the shifted
-// kernel's way (aligned loads, lane exchange, funnel shift by recv & 15), like send's (phase p), all loads
-// issued before the first wait, and the result goes back with one 16-B store at the displaced address.
-// Reading recv through aligned loads instead of one unaligned 16-B load per lane: +2.4 points (recv + 1 B)
-// and +4.8 (recv + 2 B, send + 3 B) on one box, bit-exact (profiles/r3_s2_ab_recv_phased.json).  The bytes a
-// lane takes from A[v + 1] are its own window's, so the neighbouring tile's stores never touch them.
-template <typename T, int OP>
-__global__ __launch_bounds__(64) void reduce_unaligned_kernel(const unsigned char* __restrict__ send, unsigned p,
-                                                              unsigned char* __restrict__ recv, size_t nvec,
-                                                              size_t count, int order) {
-    const size_t g = gridDim.x;
-    const unsigned pr = unsigned(reinterpret_cast<uintptr_t>(recv) & 15);
-    for (size_t t = tile_order(order, blockIdx.x, g); t * 64 < nvec; t += g) {
-        const size_t i = t * 64 + threadIdx.x;
-        const PhasedLoad xr = ld_phased_issue(recv, pr, i, nvec), xs = ld_phased_issue(send, p, i, nvec);
-        const u32x4 o = combine16<T, OP>(ld_phased_finish(xr, pr), ld_phased_finish(xs, p));
-        if (i < nvec) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_u*>(recv + 16 * i));
-    }
-    if (blockIdx.x == 0)
-        for (size_t j = nvec * Pack<T>::N + threadIdx.x; j < count; j += 64)
-            st_elem<T, false>(recv, j, Combine<T, OP>::apply(ld_elem<T, false>(recv, j), ld_elem<T, false>(send, j)));
-}
-
+// The two kernels spell their tiles and edge loops out, line for line alike: one body with a CHAIN flag behind both
+// ran the chain 0.6-2 points below the separate kernels' own band at k = 2 and k = 8 (profiles/route_fold_ab.json) and cost
+// 16-bit instances of the per-operand form up to two waves per SIMD of register-limited occupancy.
 template <typename T, int OP, int K, bool XCD, bool FIRST = false, int RUN = 1>
 __global__ __launch_bounds__(64) void reduce_multi_phased_kernel(SendList sends, PhaseList ph,
                                                                  unsigned char* __restrict__ recv, size_t head,
@@ -456,7 +450,7 @@ __global__ __launch_bounds__(64) void reduce_multi_phased_kernel(SendList sends,
             if (v < nvec) acc = ld16<true>(vr + v);
             PhasedLoad x[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) x[k] = ld_phased_issue(sends.p[k] + off, ph.p[k], v, nvec);
+            for (int k = 0; k < K; ++k) x[k] = ld_phased_issue(aligned_base(sends.p[k] + off, ph.p[k]), ph.p[k], v, nvec);
 #pragma unroll
             for (int k = 0; k < K; ++k) acc = combine16<T, OP>(acc, ld_phased_finish(x[k], ph.p[k]));
             if (v < nvec) __builtin_nontemporal_store(acc, vr + v);
@@ -497,8 +491,8 @@ __global__ __launch_bounds__(64) void reduce_chain_phased_kernel(SendList sends,
         if constexpr (FIRST) {  // every operand's loads, then the shifts and combines in chain order
             PhasedLoad x[K + 1];
 #pragma unroll
-            for (int k = 0; k < K; ++k) x[k] = ld_phased_issue(sends.p[k] + off, ph.p[k], v, nvec);
-            x[K] = ld_phased_issue(own + off, ph.p[K], v, nvec);
+            for (int k = 0; k < K; ++k) x[k] = ld_phased_issue(aligned_base(sends.p[k] + off, ph.p[k]), ph.p[k], v, nvec);
+            x[K] = ld_phased_issue(aligned_base(own + off, ph.p[K]), ph.p[K], v, nvec);
             u32x4 acc = ld_phased_finish(x[0], ph.p[0]);
 #pragma unroll
             for (int k = 1; k < K; ++k) acc = combine16<T, OP>(ld_phased_finish(x[k], ph.p[k]), acc);
@@ -529,6 +523,47 @@ __global__ __launch_bounds__(64) void reduce_chain_phased_kernel(SendList sends,
 }
 
 // ---------------------------------------------------------------------------------
+// A recv that is not element-aligned (e.g. fp32 at an odd byte address; the reference's host loop takes
+// it with a warning, internal_common.hpp:504-512, its CUDA kernel not at all).  gfx950 executes
+// global_store_dwordx4 at any byte address (unaligned_probe.hip@4f20423 checks every element), so lane i owns
+// the 16 bytes of elements [V i, V i + V) at their displaced address (V = 16 / sizeof(T)): adjacent lanes'
+// windows are disjoint and hold whole elements, so no byte is written twice.  Both operands' windows are
+// read the shifted kernel's way (aligned loads, lane exchange, funnel shift by the operand's own phase);
+// unaligned 16-B loads of recv ran 2-5 points slower, of send 7-10.  A 1 KiB tile spans 9 lines of recv,
+// one shared with the next tile: the launch takes the group-interleaved tile order (tile_order), so 7 of 8 such
+// lines meet in one L2 while the chip sweeps one front, uncapped: 85.1-85.2 % of peak, the aligned kernel's
+// rate, against 80.7-82.1 % for round 2's XCD ranges under a 24-wave cap (profiles/r3_s4_*).  The tail
+// (< V elements) is block 0's, element by element.
+//
+// grid: a multiple of 8.  Block b takes tile (b % 8) * (grid / 8) + b / 8, then strides by grid.  Lane i's
+// window is recv's elements [V i, V i + V): its 16 bytes at the displaced address are read the shifted
+// kernel's way (aligned loads, lane exchange, funnel shift by recv & 15), like send's (phase p), all loads
+// issued before the first wait, and the result goes back with one 16-B store at the displaced address.
+// Reading recv through aligned loads instead of one unaligned 16-B load per lane: +2.4 points (recv + 1 B)
+// and +4.8 (recv + 2 B, send + 3 B) on one box, bit-exact (profiles/r3_s2_ab_recv_phased.json).  The bytes a
+// lane takes from A[v + 1] are its own window's, so the neighbouring tile's stores never touch them.
+// ---------------------------------------------------------------------------------
+typedef u32x4 u32x4_u __attribute__((aligned(1)));
+
+template <typename T, int OP>
+__global__ __launch_bounds__(64) void reduce_unaligned_kernel(const unsigned char* __restrict__ send, unsigned p,
+                                                              unsigned char* __restrict__ recv, size_t nvec,
+                                                              size_t count, int order) {
+    const size_t g = gridDim.x;
+    const unsigned pr = unsigned(reinterpret_cast<uintptr_t>(recv) & 15);
+    for (size_t t = tile_order(order, blockIdx.x, g); t * 64 < nvec; t += g) {
+        const size_t i = t * 64 + threadIdx.x;
+        const PhasedLoad xr = ld_phased_issue(aligned_base(recv, pr), pr, i, nvec),
+                         xs = ld_phased_issue(aligned_base(send, p), p, i, nvec);
+        const u32x4 o = combine16<T, OP>(ld_phased_finish(xr, pr), ld_phased_finish(xs, p));
+        if (i < nvec) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_u*>(recv + 16 * i));
+    }
+    if (blockIdx.x == 0)
+        for (size_t j = nvec * Pack<T>::N + threadIdx.x; j < count; j += 64)
+            st_elem<T, false>(recv, j, Combine<T, OP>::apply(ld_elem<T, false>(recv, j), ld_elem<T, false>(send, j)));
+}
+
+// ---------------------------------------------------------------------------------
 // k-way and chain combines into a destination that is not element-aligned (reduce_unaligned_kernel's
 // scheme for K operands): lane i's window is the 16 bytes of elements [V i, V i + V) at the destination's
 // own address (one unaligned 16-B store, gfx950); every operand -- the sources, then `own` (chain) or the
@@ -548,6 +583,11 @@ struct WindowArgs {
     size_t nvec, count;
 };
 
+// The windows kernels keep their own statements of the load (ld_window tests p between its two loads; the
+// loads-first tile holds every extra vector under one lane-63 branch and its own funnel switch) and of the two
+// orders: through ld_phased_issue / fold16 / fold_elem the per-operand tile lost 2.7-4.4 points at k = 5, 16 MiB,
+// and register-limited occupancy in a quarter of its instances, the loads-first tile 0.4 points at k = 8, 1 GiB
+// (profiles/route_fold_ab.json, route_fold_resources.json).
 // One operand's window for vector v (the 16 bytes at byte phase p past aligned vector a[v]); all 64 lanes
 // call it (p is uniform).  FULL: v and lane 63's extra vector v + 1 lie inside the body (no bounds checks).
 template <bool FULL>
@@ -556,14 +596,7 @@ __device__ __forceinline__ u32x4 ld_window(const u32x4* a, unsigned p, size_t v,
     if (FULL || (p != 0 ? v <= nvec : v < nvec)) lo = __builtin_nontemporal_load(a + v);
     if (p == 0) return lo;
     if ((threadIdx.x & 63) == 63 && (FULL || v < nvec)) ex = a[v + 1];
-    const u32x4 hi = from_next_lane_or(lo, ex);
-    const unsigned b = p & 3;
-    switch (p >> 2) {  // uniform
-    case 0: return funnel16<0>(lo, hi, b);
-    case 1: return funnel16<1>(lo, hi, b);
-    case 2: return funnel16<2>(lo, hi, b);
-    default: return funnel16<3>(lo, hi, b);
-    }
+    return funnel_by(lo, from_next_lane_or(lo, ex), p);
 }
 
 template <typename T, int OP, int K, bool CHAIN, bool FULL>
@@ -668,30 +701,34 @@ __global__ __launch_bounds__(64) void reduce_windows_kernel(WindowArgs A) {
 // The round-3 forms, kept for k <= 2: every operand through ld_phased with bounds checks and a
 // runtime tile order.  At k = 2 they run 2.5-4.3 points faster than reduce_windows_kernel (83.8 / 82.1 % against
 // 79.5 / 79.6 %, destination + 2 B, sources in phase; profiles/r4_s7_ab_windows.json), which wins from k = 3.
+// One body for both orders.  k-way: own = dst = recv, whose window's loads are issued first, as
+// reduce_unaligned_kernel does; chain: own is read like a source, ph.p[K] its phase.
+template <typename T, int OP, int K, bool CHAIN>
+__device__ __forceinline__ void unaligned_body(const SendList& sends, const PhaseList& ph, const unsigned char* own,
+                                               unsigned char* dst, size_t nvec, size_t count, int order) {
+    const size_t g = gridDim.x;
+    const unsigned pr = unsigned(reinterpret_cast<uintptr_t>(dst) & 15);
+    for (size_t t = tile_order(order, blockIdx.x, g); t * 64 < nvec; t += g) {
+        const size_t i = t * 64 + threadIdx.x;
+        PhasedLoad xr{};
+        if constexpr (!CHAIN) xr = ld_phased_issue(aligned_base(dst, pr), pr, i, nvec);
+        u32x4 w[K + 1];
+#pragma unroll
+        for (int k = 0; k < K; ++k) w[k] = ld_phased(sends.p[k], ph.p[k], i, nvec);
+        w[K] = CHAIN ? ld_phased(own, ph.p[K], i, nvec) : ld_phased_finish(xr, pr);
+        const u32x4 o = fold16<T, OP, K, CHAIN>(w);
+        if (i < nvec) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_u*>(dst + 16 * i));
+    }
+    if (blockIdx.x == 0)
+        for (size_t j = nvec * Pack<T>::N + threadIdx.x; j < count; j += 64)
+            fold_elem<T, OP, K, CHAIN, false, false>(sends.p, own, dst, j);
+}
+
 template <typename T, int OP, int K>
 __global__ __launch_bounds__(64) void reduce_multi_unaligned_kernel(SendList sends, PhaseList ph,
                                                                     unsigned char* __restrict__ recv, size_t nvec,
                                                                     size_t count, int order) {
-    const size_t g = gridDim.x;
-    const unsigned pr = unsigned(reinterpret_cast<uintptr_t>(recv) & 15);
-    for (size_t t = tile_order(order, blockIdx.x, g); t * 64 < nvec; t += g) {
-        const size_t i = t * 64 + threadIdx.x;
-        const PhasedLoad xr = ld_phased_issue(recv, pr, i, nvec);  // recv's window, as reduce_unaligned_kernel
-        u32x4 s[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) s[k] = ld_phased(sends.p[k], ph.p[k], i, nvec);
-        u32x4 acc = ld_phased_finish(xr, pr);
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc = combine16<T, OP>(acc, s[k]);
-        if (i < nvec) __builtin_nontemporal_store(acc, reinterpret_cast<u32x4_u*>(recv + 16 * i));
-    }
-    if (blockIdx.x == 0)
-        for (size_t j = nvec * Pack<T>::N + threadIdx.x; j < count; j += 64) {
-            T acc = ld_elem<T, false>(recv, j);
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc = Combine<T, OP>::apply(acc, ld_elem<T, false>(sends.p[k], j));
-            st_elem<T, false>(recv, j, acc);
-        }
+    unaligned_body<T, OP, K, false>(sends, ph, recv, recv, nvec, count, order);
 }
 
 // Chain order as reduce_chain_vec_kernel; ph.p[K] is own's phase.
@@ -699,25 +736,7 @@ template <typename T, int OP, int K>
 __global__ __launch_bounds__(64) void reduce_chain_unaligned_kernel(SendList sends, PhaseList ph,
                                                                     const unsigned char* own, unsigned char* dst,
                                                                     size_t nvec, size_t count, int order) {
-    const size_t g = gridDim.x;
-    for (size_t t = tile_order(order, blockIdx.x, g); t * 64 < nvec; t += g) {
-        const size_t i = t * 64 + threadIdx.x;
-        u32x4 s[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) s[k] = ld_phased(sends.p[k], ph.p[k], i, nvec);
-        const u32x4 o = ld_phased(own, ph.p[K], i, nvec);
-        u32x4 acc = s[0];
-#pragma unroll
-        for (int k = 1; k < K; ++k) acc = combine16<T, OP>(s[k], acc);
-        if (i < nvec) __builtin_nontemporal_store(combine16<T, OP>(o, acc), reinterpret_cast<u32x4_u*>(dst + 16 * i));
-    }
-    if (blockIdx.x == 0)
-        for (size_t j = nvec * Pack<T>::N + threadIdx.x; j < count; j += 64) {
-            T acc = ld_elem<T, false>(sends.p[0], j);
-#pragma unroll
-            for (int k = 1; k < K; ++k) acc = Combine<T, OP>::apply(ld_elem<T, false>(sends.p[k], j), acc);
-            st_elem<T, false>(dst, j, Combine<T, OP>::apply(ld_elem<T, false>(own, j), acc));
-        }
+    unaligned_body<T, OP, K, true>(sends, ph, own, dst, nvec, count, order);
 }
 
 // ---------------------------------------------------------------------------------
@@ -748,79 +767,50 @@ int with_k(int k, F&& f) {
     }
 }
 
-struct Split {
-    size_t head, nvec, tail;
-};
-
-// head scalars bring recv to an `align`-byte boundary (16 or more, a power of two).  Aligning recv to
-// its 128-B lines keeps every tile's recv loads and stores whole-line: a recv that straddles lines
-// costs 10-15 % (phase_probe.py@4f20423, profiles/r1_s3_phase_probe.json).  head < align / sizeof(T).
+// Split, split_for_vectors, grid_for, phase_word: routing.hpp.
 template <typename T>
 inline Split split_for_vectors(uintptr_t recv, size_t count, size_t align = 16) {
-    constexpr size_t V = Pack<T>::N;
-    size_t head = ((align - (recv & (align - 1))) & (align - 1)) / sizeof(T);
-    if (head > count) head = count;
-    const size_t rest = count - head;
-    const size_t nvec = rest / V;
-    return Split{head, nvec, rest - nvec * V};
-}
-
-// One block per `tile` vectors; a split with no whole vector still needs block 0 for its head / tail elements.
-inline size_t grid_for(Split sp, size_t tile) {
-    const size_t grid = ceil_div(sp.nvec, tile);
-    return grid == 0 && sp.head + sp.tail > 0 ? 1 : grid;
+    return split_for_vectors(recv, count, sizeof(T), align);
 }
 
 template <typename T, int OP, typename C>
-int launch_vec(const unsigned char* s, unsigned char* r, Split sp, hipStream_t stream, size_t grid_cap = 0,
-               size_t lds_bytes = 0) {
+int launch_vec(const unsigned char* s, unsigned char* r, Split sp, hipStream_t stream, size_t grid_cap = 0) {
     size_t grid = grid_for(sp, C::TILE);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&s, &r, &sp.head, &sp.nvec, &sp.tail};
-    return launch(reinterpret_cast<const void*>(&reduce_vec_kernel<T, OP, C>), grid, args, stream, C::BLOCK,
-                  lds_bytes);
+    return launch(reinterpret_cast<const void*>(&reduce_vec_kernel<T, OP, C>), grid, args, stream, C::BLOCK);
 }
 
 // Element-aligned operands with different 16-B phases (or an element-aligned recv and a send at any byte
 // address, SEND_ALIGNED false): the shifted vector kernel.
 template <typename T, int OP, int POLICY, bool XCD, int TAG = 0, bool SEND_ALIGNED = true, int RUN = 1>
 int launch_shift(const unsigned char* s, unsigned char* r, size_t count, hipStream_t stream, size_t align = 16,
-                 size_t lds_bytes = 0, size_t grid_cap = 0) {
+                 size_t grid_cap = 0) {
     Split sp = split_for_vectors<T>(reinterpret_cast<uintptr_t>(r), count, align);
-    unsigned p = unsigned((reinterpret_cast<uintptr_t>(s) + sp.head * sizeof(T)) & 15);
+    unsigned p = phase_word(s, sp.head * sizeof(T));
     size_t grid = grid_for(sp, 64);
     if (grid_cap && grid > grid_cap) grid = grid_cap;
     void* args[] = {&s, &r, &sp.head, &sp.nvec, &sp.tail, &p};
     return launch(reinterpret_cast<const void*>(&reduce_shift_kernel<T, OP, POLICY, XCD, TAG, SEND_ALIGNED, RUN>), grid,
-                  args, stream, 64, lds_bytes);
+                  args, stream, 64);
 }
 
-// 16-B phase of an operand whose body starts `off` bytes in (see PhaseList).
-inline unsigned phase_word(const unsigned char* base, size_t off) {
-    return unsigned((reinterpret_cast<uintptr_t>(base) + off) & 15);
-}
-
-// The phased k-way and chain launches, instantiated for every (T, OP) in phased_multi.hip and
-// phased_chain.hip (their own translation units, so they compile beside local_reduce.hip).
-template <typename T, int OP>
-int multi_phased_typed(SendList sl, PhaseList ph, int nsend, unsigned char* r, Split sp, hipStream_t stream);
+// The launches below take the k-way combine as own = d = recv.
+// The phased k-way and chain launches, defined in phased_launch.hpp and instantiated for every (T, OP) in
+// phased_multi.hip (CHAIN false) and phased_chain.hip (CHAIN true): their own translation units, so they compile
+// beside local_reduce.hip.
+template <typename T, int OP, bool CHAIN>
+int phased_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d, Split sp,
+                 hipStream_t stream);
 // In-phase k-way and chain launches whose sources straddle recv's 128-B lines: sources loaded
 // through the caches (the pairwise StraddleCfg rule), instantiated in the same translation units.
-template <typename T, int OP>
-int multi_straddle_typed(SendList sl, int nsend, unsigned char* r, Split sp, hipStream_t stream);
-template <typename T, int OP>
-int chain_straddle_typed(SendList sl, int nsend, const unsigned char* own, unsigned char* d, Split sp,
-                         hipStream_t stream);
-template <typename T, int OP>
-int chain_phased_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d, Split sp,
-                       hipStream_t stream);
+template <typename T, int OP, bool CHAIN>
+int straddle_typed(SendList sl, int nsend, const unsigned char* own, unsigned char* d, Split sp, hipStream_t stream);
 // k-way (2 <= nsend <= 8) and chain (1 <= nsend <= 8) combines into a destination that is not
 // element-aligned, instantiated for every (T, OP) in unaligned_multi.hip.  ph.p[k] = sends[k] & 15
 // (and ph.p[nsend] = own & 15 for the chain).
-template <typename T, int OP>
-int multi_unaligned_typed(SendList sl, PhaseList ph, int nsend, unsigned char* r, size_t count, hipStream_t stream);
-template <typename T, int OP>
-int chain_unaligned_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d,
-                          size_t count, hipStream_t stream);
+template <typename T, int OP, bool CHAIN>
+int unaligned_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d, size_t count,
+                    hipStream_t stream);
 
 }  // namespace dccl_amd

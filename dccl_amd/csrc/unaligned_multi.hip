@@ -100,32 +100,24 @@ int launch_windows(const SendList& sl, const PhaseList& ph, const unsigned char*
 
 }  // namespace
 
-template <typename T, int OP>
-int multi_unaligned_typed(SendList sl, PhaseList ph, int nsend, unsigned char* r, size_t count, hipStream_t stream) {
+// own = d for the k-way combine (2..8 sources; one source is the pairwise combine), the chain has 1..8.
+template <typename T, int OP, bool CHAIN>
+int unaligned_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d, size_t count,
+                    hipStream_t stream) {
+    constexpr int LO = CHAIN ? 1 : 2;
     if (round3_form(ph, nsend))
-        return with_k<2, 2>(nsend, [&](auto K) {
-            return launch_round3<T, OP, K.value, false>(sl, ph, nullptr, r, count, stream);
+        return with_k<LO, 2>(nsend, [&](auto K) {
+            return launch_round3<T, OP, K.value, CHAIN>(sl, ph, own, d, count, stream);
         });
-    return with_k<2, 8>(nsend, [&](auto K) {
-        return launch_windows<T, OP, K.value, false>(sl, ph, nullptr, r, count, stream);
-    });
-}
-
-template <typename T, int OP>
-int chain_unaligned_typed(SendList sl, PhaseList ph, int nsend, const unsigned char* own, unsigned char* d,
-                          size_t count, hipStream_t stream) {
-    if (round3_form(ph, nsend))
-        return with_k<1, 2>(nsend, [&](auto K) {
-            return launch_round3<T, OP, K.value, true>(sl, ph, own, d, count, stream);
-        });
-    return with_k<1, 8>(nsend, [&](auto K) {
-        return launch_windows<T, OP, K.value, true>(sl, ph, own, d, count, stream);
+    return with_k<LO, 8>(nsend, [&](auto K) {
+        return launch_windows<T, OP, K.value, CHAIN>(sl, ph, own, d, count, stream);
     });
 }
 
 #define DCCL_UNALIGNED_INST_OP(T, OP)                                                                             \
-    template int multi_unaligned_typed<T, OP>(SendList, PhaseList, int, unsigned char*, size_t, hipStream_t);      \
-    template int chain_unaligned_typed<T, OP>(SendList, PhaseList, int, const unsigned char*, unsigned char*, size_t, \
+    template int unaligned_typed<T, OP, false>(SendList, PhaseList, int, const unsigned char*, unsigned char*, size_t, \
+                                               hipStream_t);                                                       \
+    template int unaligned_typed<T, OP, true>(SendList, PhaseList, int, const unsigned char*, unsigned char*, size_t, \
                                               hipStream_t);
 #define DCCL_UNALIGNED_INST(T)              \
     DCCL_UNALIGNED_INST_OP(T, kSum)         \

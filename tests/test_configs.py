@@ -12,8 +12,8 @@ C5  one 16 GiB-per-operand fp32 Sum buffer split into 1, 2, 4 and 8 contiguous 2
 Beyond one grid  17 GiB per operand (more tiles than the 2^24-block grid cap, so every kernel's grid-stride
     loop runs): the aligned, shifted and misaligned-recv combines, the whole result checked on the device
     against the synthetic inputs regenerated per 1 GiB slice.
-Straddle  in-phase k-way and chain sources off the destination's 128-B line grid (multi_straddle_typed,
-    chain_straddle_typed; advisor r1): sources at 16-B multiples that are not 128-B multiples, the
+Straddle  in-phase k-way and chain sources off the destination's 128-B line grid (straddle_typed, both
+    orders; advisor r1): sources at 16-B multiples that are not 128-B multiples, the
     destination at another line offset, odd counts, k = 1..8, every dtype, against the sequential and
     chain-order oracle.
 """

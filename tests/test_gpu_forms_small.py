@@ -65,7 +65,13 @@ EXPECTED_CASES = {
     "windows_chain": _ROFFS * len(WINDOWS_SRC) * len(WINDOWS_OWN),
     "routed": SLOTS * len(SHAPES) * 2 * (len(ROUTED_SRC) + len(ROUTED_CHAIN)),
     "size_rows": 2 * 3 * len(ROW_BYTES) * len(ROW_CLASSES) * 3,
+    "windows_first_sweep": 2 * 2 * 16,
 }
+# windows_first_sweep: the loads-first window tile (tuned off-phase form at K = 5) with source 0, and the chain's
+# own, at every byte phase 0..15; the other sources at phase 4, so every case is the off-phase class
+SWEEP_SHAPE = ("tuned", TUNED[1])
+SWEEP_K = 5
+SWEEP_DTS = [7, 9]
 
 
 def esz_of(dt):
@@ -86,6 +92,14 @@ def plan(family):
     """The cases of a family, without data: dicts of form, k, dt, shape, count and the placement names.  The
     dtype cycles with the slot and the shape, so every (k, dtype) and every (dtype, size) pair occurs."""
     cases = []
+    if family == "windows_first_sweep":
+        for form in ("multi", "chain"):
+            for dt in SWEEP_DTS:
+                for phase in range(16):
+                    cases.append(dict(form=form, k=SWEEP_K, dt=dt, shape=SWEEP_SHAPE, count=count_of(SWEEP_SHAPE, dt),
+                                      roff=1, src="sweep", own="own_sweep" if form == "chain" else "none",
+                                      phase=phase))
+        return cases
     if family == "size_rows":
         for form, ks in ROW_K.items():
             for ki, k in enumerate(ks):
@@ -133,6 +147,8 @@ def source_offsets(rng, case):
         ph = [int(rng.choice(BYTE_PHASES)) for _ in range(k)]
         if not any(ph):
             ph[int(rng.integers(k))] = int(rng.choice(BYTE_PHASES[1:]))
+    elif src == "sweep":  # source 0 at the case's byte phase, the others at phase 4
+        ph = [case["phase"]] + [4] * (k - 1)
     elif src == "byte1":  # not element-aligned
         ph = [1] * k
     elif src == "in_phase":  # the destination's own 16-B phase, on its 128-B lines
@@ -197,7 +213,8 @@ def run_cases(cases, rng, check_sources=False):
             td, pd = dev_bytes(r, roff)
             po = pd
         else:  # a separate own; the destination starts as zeros
-            ooff = {"own0": 0, "own4": 4, "own_in_phase": roff % 16 + 32, "own_only_off": (roff + esz) % 16 + 32}[own]
+            ooff = {"own0": 0, "own4": 4, "own_in_phase": roff % 16 + 32, "own_only_off": (roff + esz) % 16 + 32,
+                    "own_sweep": case.get("phase", 0)}[own]
             to, po = dev_bytes(r, ooff)
             td, pd = dev_bytes(np.zeros_like(r), roff)
         if form == "multi":
@@ -223,6 +240,10 @@ def run_cases(cases, rng, check_sources=False):
 
 def run_family(family):
     """In the child: every case of plan(family) on the GPU; returns (cases run, failures)."""
+    if family == "windows_first_sweep":
+        ran, bad, pairs_k, _ = run_cases(plan(family), np.random.default_rng(7100))
+        assert pairs_k == {(form, SWEEP_K, dt) for form in ("multi", "chain") for dt in SWEEP_DTS}
+        return ran, bad
     rng = np.random.default_rng(7000 + sorted(FAMILY_KS).index(family))
     ran, bad, pairs_k, pairs_size = run_cases(plan(family), rng)
     # the plan really met every (k, dtype) and (dtype, size) pair
@@ -271,7 +292,7 @@ def test_shift_is_zero_in_the_suite_process(gpu):
     assert dccl_amd.lib.dccl_caps_test_shift() == 0
 
 
-@pytest.mark.parametrize("family", ["windows_kway", "windows_chain", "routed", "size_rows"])
+@pytest.mark.parametrize("family", ["windows_kway", "windows_chain", "routed", "size_rows", "windows_first_sweep"])
 def test_size_selected_forms_at_small_sizes(gpu, family):
     """windows_kway / windows_chain: a destination that is not element-aligned (offset 1, and 33 + sizeof(T) / 2),
     sources all at 16-B phase 0 (the in-phase class), all at phase 4, at mixed byte phases and with exactly one
@@ -283,7 +304,9 @@ def test_size_selected_forms_at_small_sizes(gpu, family):
     phased k-way (k = 2, 5, 8) and chain (k = 1, 4, 8) launches just above 24, 48 and 96 KiB with head and tail
     scalars and a partial last tile: each carries the larger LDS request of its caps::kWaves row and must return
     0 and the exact result (at 96 KiB the phased k-way k = 5 and chain k = 4 launches are routed to
-    reduce_windows_kernel, as at 96 MiB)."""
+    reduce_windows_kernel, as at 96 MiB).  windows_first_sweep: the loads-first window tile (k = 5, 6145 vectors,
+    destination at offset 1, fp32 and bf16) with source 0, and the chain's separate own, at every byte phase
+    0..15 and the other sources at phase 4: the funnel shift at every byte count in that tile."""
     env = {**os.environ, "DCCL_CAPS_TEST_SHIFT": str(SHIFT), "PYTHONPATH": ROOT}
     t0 = time.monotonic()
     p = subprocess.run([sys.executable, "-c", CHILD, ROOT, family, str(SHIFT)], env=env, capture_output=True,

@@ -364,6 +364,48 @@ def test_multi_mixed_phases(dccl, k):
             assert fp_equal(host_of(tr, roff, r), want, dt), (k, dt, n, op, offs, roff)
 
 
+@pytest.mark.parametrize("form,k", [("multi", 2), ("multi", 5), ("chain", 2), ("chain", 5), ("chain", 6)])
+def test_every_byte_phase(dccl, form, k):
+    """Source 0 (and, for the chain, a separate own) at every byte phase 0..15, the other sources at phase 0:
+    the shifted load's funnel at every byte count, in the XCD per-operand (k = 2), loads-first (k = 5) and plain
+    per-operand (chain k = 6) phased kernels and in the windows kernels.  fp32 and bf16; the destination one
+    element past a 128-B line (head scalars up to the next line, 133 vectors, V - 1 tail scalars) and one byte
+    past a line (133 windows and V - 1 tail elements).  Bit for bit against the oracle in the documented order;
+    nothing outside the destination written."""
+    rng = np.random.default_rng(4400 + 10 * k + (form == "chain"))
+    for dt in (7, 9):
+        esz = int(oracle.NP_DTYPES[dt]().itemsize)
+        v = 16 // esz
+        for roff, n in ((128 + esz, (128 - esz) // esz + 133 * v + v - 1), (128 + 1, 133 * v + v - 1)):
+            op = int(rng.integers(0, 4))
+            sends = [rand_inputs(rng, dt, n)[0] for _ in range(k)]
+            _, r = rand_inputs(rng, dt, n)
+            if form == "multi":  # recv = op(...op(op(recv, s0), s1)..., s{k-1})
+                want = r
+                for x in sends:
+                    want = expected(x, want, dt, op)
+            else:  # dst = op(own, op(s{k-1}, ... op(s1, s0)))
+                acc = sends[0]
+                for x in sends[1:]:
+                    acc = expected(acc, x, dt, op)
+                want = expected(acc, r, dt, op)
+            others = [dev_bytes(x, 0) for x in sends[1:]]
+            for phase in range(16):
+                first = dev_bytes(sends[0], phase)
+                sptrs = [first[1]] + [h[1] for h in others]
+                if form == "multi":
+                    td, pd = dev_bytes(r, roff)
+                    rc = dccl.local_reduce_multi(sptrs, pd, dt, n, op, 0)
+                else:
+                    to, po = dev_bytes(r, phase)
+                    td, pd = dev_bytes(np.zeros_like(r), roff)
+                    rc = dccl.local_reduce_chain(sptrs, po, pd, dt, n, op, 0)
+                assert rc == 0
+                torch.cuda.synchronize()
+                assert fp_equal(host_of(td, roff, r), want, dt), (form, k, dt, op, roff, phase)
+                assert not td[:roff].any() and not td[roff + n * esz:].any(), (form, k, dt, roff, phase)
+
+
 @pytest.mark.parametrize("k", [2, 3, 5, 8])
 def test_multi_byte_offsets(dccl, k):
     """Sources at any byte address (phased kernel with byte phases, sources' head / tail read bytewise) and

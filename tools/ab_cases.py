@@ -6,6 +6,10 @@ launches per round, the median over --rounds rounds reported per library; each c
 compared bit for bit between the two libraries at the timed count (so at the size whose dispatch is timed).
 
     python tools/ab_cases.py LIB_A LIB_B [--cases pair_dst+1,multi4_dst+2] [--rounds 5] [--out f.json]
+
+--a-twice times library A a second time after B in every round (A, B, A), so A's own min..max band over
+2 x rounds values can be formed; the JSON then carries every round's value of both libraries and says whether
+B's median lies inside that band or below it.
 """
 import argparse
 import ctypes
@@ -89,6 +93,7 @@ def main():
     p.add_argument("--launches", type=int, default=10)
     p.add_argument("--mib", type=int, default=1024)
     p.add_argument("--out", default="")
+    p.add_argument("--a-twice", action="store_true", help="per round time A, B, A: A's own band")
     p.add_argument("--all-k", default="", help="comma-separated case stems expanded over k = 2..8, e.g. multi,chain_strad")
     a = p.parse_args()
     libs = [bind(x) for x in a.libs]
@@ -131,7 +136,7 @@ def main():
     for _ in range(a.rounds):
         for name in names:
             k, call = table[name]
-            for i, lib in enumerate(libs):
+            for i, lib in [(0, libs[0]), (1, libs[1])] + ([(0, libs[0])] if a.a_twice else []):
                 assert call(lib, n, st) == 0
                 ev0.record()
                 for _ in range(a.launches):
@@ -145,10 +150,14 @@ def main():
         fr = [round((k + 2) * n * 4 / (statistics.median(times[(name, i)]) * 1e-3) / PEAK, 4) for i in range(2)]
         rows.append({"case": name, "k": k, "frac_a": fr[0], "frac_b": fr[1], "delta_points": round(100 * (fr[1] - fr[0]), 2),
                      "bit_exact_b_vs_a": exact[name]})
+        ua, ub = ([round(1e3 * x, 2) for x in times[(name, i)]] for i in range(2))  # us per launch, every round
+        rows[-1].update({"us_a_rounds": ua, "us_b_rounds": ub, "us_a_band": [min(ua), max(ua)],
+                         "us_b_median": round(statistics.median(ub), 2),
+                         "b_median_in_or_below_a_band": statistics.median(ub) <= max(ua)})
         print(f"{name:22s} A {100 * fr[0]:6.2f}%  B {100 * fr[1]:6.2f}%  ({100 * (fr[1] - fr[0]):+.2f})  exact {exact[name]}",
               flush=True)
     res = {"libs": a.libs, "bytes_per_operand": nbytes, "count": n, "rounds": a.rounds, "launches": a.launches,
-           "rows": rows}
+           "a_twice": a.a_twice, "rows": rows}
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
