@@ -29,6 +29,7 @@
 
 #include "dccl/dccl.hpp"
 #include "dccl/dccl_reduce.h"
+#include "select.hpp"
 
 namespace dccl_amd {
 
@@ -97,7 +98,7 @@ private:
 //   kWideScaledSum  dcclRedOpCreateWideScaledSum: the scalar is ONE fp32, times the finished fp32 accumulator
 // Readers switch on `kind` or ask the accessor named for their question, never the scalar's storage.  A host-immediate
 // scalar lives in `bits`: a copy of the form (a queued call, a packed run) is complete, and its scalar() valid as long.
-enum SumKind : int { kBuiltin = 0, kPremulSum, kWideSum, kWideScaledSum };
+// (SumKind itself is in select.hpp, which has no HIP include.)
 struct SumForm {
     SumKind kind = kBuiltin;
     uint64_t bits = 0;              // the scalar's bytes, read at creation (ncclScalarHostImmediate)

@@ -29,7 +29,6 @@
 #include <string>
 #include <vector>
 
-
 #include "algorithms.hpp"
 #include "bootstrap.hpp"
 #include "comm.hpp"
@@ -279,48 +278,15 @@ long env_long(const char* a, const char* b, long dflt) {
     return v ? std::strtol(v, nullptr, 10) : dflt;
 }
 
-bool rccl_requested() {
-    const char* t = std::getenv("DCCL_TRANSPORT");
-    return t != nullptr && std::string(t) == "rccl";
-}
+// The one read of DCCL_ALLREDUCE_ALGORITHM: every validator keeps the name in its Call, and the call runs by it.
+static_assert(parse_algo(DCCL_ALLREDUCE_RING) == AlgoName::kRing &&
+              parse_algo(DCCL_ALLREDUCE_RABENSEIFNER) == AlgoName::kRabenseifner, "select.hpp spells the names");
+AlgoName algo_name() { return parse_algo(std::getenv(DCCL_ALLREDUCE_ALGORITHM_CONFSTR)); }
 
-bool ipc_requested() {
-    const char* t = std::getenv("DCCL_TRANSPORT");
-    return t != nullptr && std::string(t) == "ipc";
-}
-
-enum class Algorithm { kRing, kRabenseifner, kDirect, kUnknown };
-
-// DCCL_ALLREDUCE_ALGORITHM (the reference's DCCL/allreduce_algorithm key, dccl.hpp:38-46): auto
-// (default: the direct collectives for device buffers of an in-process group, direct_selected(), and
-// the ring otherwise), ring, rabenseifner, or direct.  The reference defaults to ring and silently
-// skips the reduction for any other value (dccl.cpp:412-501); here that is ncclInvalidUsage.
-Algorithm allreduce_algorithm() {
-    const char* a = std::getenv(DCCL_ALLREDUCE_ALGORITHM_CONFSTR);
-    if (a == nullptr || *a == 0 || std::string(a) == DCCL_ALLREDUCE_RING || std::string(a) == "auto")
-        return Algorithm::kRing;
-    if (std::string(a) == DCCL_ALLREDUCE_RABENSEIFNER) return Algorithm::kRabenseifner;
-    if (std::string(a) == "direct" || std::string(a) == "grouped") return Algorithm::kDirect;
-    return Algorithm::kUnknown;
-}
-
-// The grouped forms of algorithms.hpp on the RCCL transport's device buffers, when DCCL_ALLREDUCE_ALGORITHM
-// is "grouped" ("direct" keeps its meaning: the peer-read collectives of in-process and IPC groups; on RCCL it
-// runs the ring).  Results are the ring's bit for bit.  Not the default yet: on the one-GPU
-// rehearsal (4 RCCL ranks over loopback sockets) a 64 MiB all-reduce took 28 ms grouped against 16 ms for the
-// ring, while its combine time per collective fell from 45 to 22 us; the xGMI mesh, where
-// the grouped form's W - 1 concurrent transfers use W - 1 links, is measured by the driver's 8-GPU bench.
-bool grouped_selected(const dcclComm* c, bool device) {
-    if (!device || c->rccl == nullptr || c->world < 2) return false;
-    const char* a = std::getenv(DCCL_ALLREDUCE_ALGORITHM_CONFSTR);
-    if (a == nullptr) return false;
-    return std::string(a) == "grouped";
-}
-
-uint32_t floor_log2_u32(uint32_t n) {
-    uint32_t k = 0;
-    while ((n >> (k + 1)) != 0) ++k;
-    return k;
+Transport transport_of(const dcclComm* c) {
+    if (c->ipc != nullptr) return Transport::kIpc;
+    if (c->rccl != nullptr) return Transport::kRccl;
+    return c->p2p != nullptr ? Transport::kP2p : Transport::kThreads;
 }
 
 // Which buffers the communicator's transport can move: the in-process channels both; the IPC transport
@@ -337,16 +303,14 @@ namespace dccl {
 
 ncclResult_t ncclCommInit(ncclComm_t* comm) {
     if (comm == nullptr) return ncclInvalidArgument;
-    const long w = env_long("DCCL_WORLD_SIZE", (rccl_requested() || ipc_requested()) ? "WORLD_SIZE" : nullptr, 1);
+    const char* t = std::getenv("DCCL_TRANSPORT");
+    const bool ipc = t != nullptr && std::string(t) == "ipc", rccl = t != nullptr && std::string(t) == "rccl";
+    const long w = env_long("DCCL_WORLD_SIZE", (rccl || ipc) ? "WORLD_SIZE" : nullptr, 1);
     if (w <= 0) return ncclInvalidArgument;
-    if (ipc_requested()) {
+    if (rccl || ipc) {  // one process per GPU: rank / world from the launcher's environment
         const long r = env_long("DCCL_RANK", "RANK", 0);
         if (r < 0 || r >= w) return ncclInvalidArgument;
-        return dcclCommInitIpc(comm, static_cast<uint32_t>(w), static_cast<uint32_t>(r));
-    }
-    if (rccl_requested()) {  // one process per GPU: rank / world from the launcher's environment
-        const long r = env_long("DCCL_RANK", "RANK", 0);
-        if (r < 0 || r >= w) return ncclInvalidArgument;
+        if (ipc) return dcclCommInitIpc(comm, static_cast<uint32_t>(w), static_cast<uint32_t>(r));
         unsigned char id[kRcclUniqueIdBytes];
         ncclResult_t rc = bootstrap_unique_id(static_cast<uint32_t>(r), static_cast<uint32_t>(w), id);
         if (rc != ncclSuccess) return rc;
@@ -400,10 +364,7 @@ ncclResult_t ncclCommFinalize(ncclComm_t comm) {
     } else if (comm->group != nullptr) {
         comm->group->barrier();  // no peer may still be reading our buffers
     }  // a plugged-in p2p transport belongs to the caller
-    for (hipEvent_t e : comm->ready_events)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : comm->done_events)
-        if (e) (void)hipEventDestroy(e);
+    destroy_events(comm);
     if (comm->dev_scratch) (void)hipFree(comm->dev_scratch);
     if (comm->dev_work) (void)hipFree(comm->dev_work);
     if (comm->dev_pack) (void)hipFree(comm->dev_pack);
@@ -467,9 +428,15 @@ struct Call {
     SumForm form;              // resolved: which sum, with its scalar by value (comm.hpp)
     int root = 0;
     bool dev = false;
-    Algorithm algo = Algorithm::kRing;  // ncclAllReduce: DCCL_ALLREDUCE_ALGORITHM when the call was validated
+    AlgoName algo = AlgoName::kAuto;  // DCCL_ALLREDUCE_ALGORITHM when the call was validated: the call runs by it
     hipStream_t stream = nullptr;
 };
+
+// What the call does when it runs (select.hpp).  By value from the Call alone: a queued call takes at ncclGroupEnd
+// the path its count was checked for, whatever the environment says by then.
+Path path_of(const Call& c) {
+    return select(c.api, transport_of(c.comm), c.comm->world, c.dev, c.form.kind, c.algo);
+}
 
 // The buffer checks every validator shares: the two buffers' one placement, a user op on device buffers only (its
 // scaling / widening kernels run on the GPU), and a transport that moves such buffers.
@@ -481,8 +448,11 @@ ncclResult_t check_buffers(const dcclComm* comm, const void* a, const void* b, c
 }
 
 // The fields every collective has, by name; the validators write the rest where they learn it (user_op / op / form
-// from resolve_op, dev from check_buffers, root, algo).  Their `c` comes in default-constructed.
-void set_call(Call* c, int api, ncclComm_t comm, const void* send, void* recv, size_t count, int dtype) {
+// from resolve_op, dev from check_buffers, root).  Their `c` comes in default-constructed, and only a call with
+// something to do gets here: a Call whose comm is still null has nothing to run.
+void set_call(Call* c, int api, ncclComm_t comm, const void* send, void* recv, size_t count, int dtype,
+              AlgoName algo = algo_name()) {
+    c->algo = algo;
     c->api = api;
     c->comm = comm;
     c->send = send;
@@ -497,9 +467,8 @@ void set_call(Call* c, int api, ncclComm_t comm, const void* send, void* recv, s
 // validate + queue, and the outermost ncclGroupEnd runs the queue (below).
 // ------------------------------------------------------------------------------------------
 ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                         ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
+                         ncclRedOp_t user_op, ncclComm_t comm, Call* c) {
     validate_comm(comm, "ncclAllReduce");
-    *todo = false;
     c->user_op = c->op = user_op;
     ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
@@ -507,65 +476,46 @@ ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncc
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     const uint32_t W = comm->world;
-    const Algorithm algo = allreduce_algorithm();  // dccl.cpp:412-413,454
-    if (algo == Algorithm::kUnknown) return ncclInvalidUsage;
-    if (algo == Algorithm::kRabenseifner && comm->ipc != nullptr) return ncclInvalidUsage;
-    if (W > 1 && algo == Algorithm::kRabenseifner && count % (1u << floor_log2_u32(W)))
+    const AlgoName algo = algo_name();  // dccl.cpp:412-413,454
+    const bool rab = algo == AlgoName::kRabenseifner;
+    if (algo == AlgoName::kUnknown) return ncclInvalidUsage;
+    if (rab && comm->ipc != nullptr) return ncclInvalidUsage;
+    if (W > 1 && rab && count % slots(Path::kRabenseifner, W))
         return ncclInvalidArgument;  // all_reduce_recursive_halving_and_doubling.cpp:50-54
-    if (W > 1 && algo != Algorithm::kRabenseifner && (count < W || count % W)) return ncclInvalidArgument;
-    set_call(c, group::kAllReduce, comm, sendbuff, recvbuff, count, datatype);
-    c->algo = algo;
-    *todo = true;
+    if (W > 1 && !rab && (count < W || count % W)) return ncclInvalidArgument;
+    set_call(c, group::kAllReduce, comm, sendbuff, recvbuff, count, datatype, algo);
     return ncclSuccess;
 }
 
-// True when ar_run's dispatch below ends in all_reduce_rabenseifner for this call: the name alone does not decide,
-// the direct forms come first.  run_packed cuts its buffer into the slots of the algorithm that RUNS.
-bool runs_rabenseifner(const Call& c) {
-    const ncclComm_t comm = c.comm;
-    if (c.api != group::kAllReduce || c.algo != Algorithm::kRabenseifner || comm->world <= 1) return false;
-    if (c.dev && direct_selected(comm)) return false;
-    if (!c.dev && host_direct_selected(comm, c.count * size_of_dtype(c.dtype) / comm->world)) return false;
-    return true;
-}
+ncclResult_t wide_staged(const Call& c);  // below: a wide sum outside the direct paths
 
-ncclResult_t wide_staged(const Call& c, hipStream_t stream);  // below: a wide sum outside the direct paths
-
-ncclResult_t ar_run(const Call& c, hipStream_t stream) {
-    const ncclComm_t comm = c.comm;
-    const void* sendbuff = c.send;
-    void* recvbuff = c.recv;
-    const size_t count = c.count;
-    const int datatype = c.dtype, op = c.op;
-    const SumForm& form = c.form;
-    const bool dev = c.dev;
-    const Algorithm algo = c.algo;
-    const size_t total = count * size_of_dtype(datatype);
-    const uint32_t W = comm->world;
-    ncclResult_t rc;
-    if (W > 1 && dev && direct_selected(comm))
-        return direct_all_reduce(comm, sendbuff, recvbuff, count, datatype, op, stream, form);
-    if (W > 1 && !dev && host_direct_selected(comm, total / W))
-        return direct_all_reduce_host(comm, sendbuff, recvbuff, count, datatype, op);
-    if (form.wide()) return wide_staged(c, stream);
-    if (W > 1 && algo != Algorithm::kRabenseifner && form.kind == kBuiltin && grouped_selected(comm, dev))
-        return all_reduce_grouped(comm, sendbuff, recvbuff, count, datatype, op, stream);
-    rc = stage_input(recvbuff, sendbuff, count, datatype, form, dev, stream);  // dccl.cpp:393-408
-    if (rc != ncclSuccess) return rc;
-    if (W == 1) return ncclSuccess;
-    void* scratch = nullptr;
-    if (runs_rabenseifner(c)) {  // scratchpad of half the buffer (dccl.cpp:458-466)
-        if ((rc = ring_scratch(comm, total / 2, dev, &scratch)) != ncclSuccess) return rc;
-        return all_reduce_rabenseifner(comm, recvbuff, scratch, count, datatype, op, dev, stream);
+ncclResult_t ar_run(const Call& c) {
+    dcclComm* comm = c.comm;
+    const Path path = path_of(c);
+    switch (path) {
+    case Path::kDirect:
+        return direct_all_reduce(comm, c.send, c.recv, c.count, c.dtype, c.op, c.stream, c.form);
+    case Path::kHostDirect: return direct_all_reduce_host(comm, c.send, c.recv, c.count, c.dtype, c.op);
+    case Path::kWideStaged: return wide_staged(c);
+    case Path::kGrouped: return all_reduce_grouped(comm, c.send, c.recv, c.count, c.dtype, c.op, c.stream);
+    case Path::kLocal:
+    case Path::kRabenseifner:
+    case Path::kRing: break;
     }
-    if ((rc = ring_scratch(comm, total / W, dev, &scratch)) != ncclSuccess) return rc;
-    return all_reduce_ring(comm, recvbuff, scratch, count, datatype, op, dev, stream);
+    ncclResult_t rc = stage_input(c.recv, c.send, c.count, c.dtype, c.form, c.dev, c.stream);  // dccl.cpp:393-408
+    if (rc != ncclSuccess || path == Path::kLocal) return rc;
+    // scratchpad: half the buffer for Rabenseifner (dccl.cpp:458-466), one slot for the ring
+    const bool rab = path == Path::kRabenseifner;
+    const size_t total = c.count * size_of_dtype(c.dtype);
+    void* scratch = nullptr;
+    if ((rc = ring_scratch(comm, rab ? total / 2 : total / comm->world, c.dev, &scratch)) != ncclSuccess) return rc;
+    return rab ? all_reduce_rabenseifner(comm, c.recv, scratch, c.count, c.dtype, c.op, c.dev, c.stream)
+               : all_reduce_ring(comm, c.recv, scratch, c.count, c.dtype, c.op, c.dev, c.stream);
 }
 
 ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
-                         ncclRedOp_t user_op, ncclComm_t comm, Call* c, bool* todo) {
+                         ncclRedOp_t user_op, ncclComm_t comm, Call* c) {
     validate_comm(comm, "ncclReduceScatter");
-    *todo = false;
     c->user_op = c->op = user_op;
     ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
@@ -573,48 +523,47 @@ ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount,
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype);
-    *todo = true;
     return ncclSuccess;
 }
 
-ncclResult_t rs_run(const Call& c, hipStream_t stream) {
-    const ncclComm_t comm = c.comm;
-    const void* sendbuff = c.send;
-    void* recvbuff = c.recv;
-    const size_t recvcount = c.count;
-    const int datatype = c.dtype, op = c.op;
-    const SumForm& form = c.form;
-    const bool dev = c.dev;
-    ncclResult_t rc;
-    const uint32_t W = comm->world, r = comm->rank;
-    const size_t slot = recvcount * size_of_dtype(datatype), total = slot * W;
-    if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce_scatter(comm, sendbuff, recvbuff, recvcount, datatype, op, stream, form);
-    if (W > 1 && !dev && host_direct_selected(comm, slot))
-        return direct_reduce_scatter_host(comm, sendbuff, recvbuff, recvcount, datatype, op);
-    if (form.wide()) return wide_staged(c, stream);
-    // slot r, reduced straight from sendbuff: no work copy (a pre-multiplied sum scales into the work copy: the ring)
-    if (W > 1 && form.kind == kBuiltin && grouped_selected(comm, dev))
-        return reduce_scatter_grouped(comm, sendbuff, recvbuff, recvcount * W, datatype, op, stream, 0);
-    if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
-    void* work = dev ? comm->dev_work : comm->host_work;
-    rc = stage_input(work, sendbuff, recvcount * W, datatype, form, dev, stream);  // dccl.cpp:585-609
+// The ring reduce-scatter of ncclReduceScatter and ncclReduce on `buf` (`count` elements, already staged), with the
+// reference's rank maps (dccl.cpp:551-698): slot o ends up reduced on rank o.
+ncclResult_t ring_to_own_slot(const Call& c, void* buf, size_t count) {
+    const uint32_t W = c.comm->world;
+    void* scratch = nullptr;
+    const ncclResult_t rc = ring_scratch(c.comm, count / W * size_of_dtype(c.dtype), c.dev, &scratch);
     if (rc != ncclSuccess) return rc;
-    if (W > 1) {
-        void* scratch = nullptr;
-        if ((rc = ring_scratch(comm, slot, dev, &scratch)) != ncclSuccess) return rc;
-        rc = reduce_scatter_ring(comm, work, scratch, recvcount * W, datatype, op, dev, stream,
-                                 [W](uint32_t o) { return (o + W - 1) % W; },
-                                 [W](uint32_t n) { return (n + 1) % W; });
-        if (rc != ncclSuccess) return rc;
+    return reduce_scatter_ring(c.comm, buf, scratch, count, c.dtype, c.op, c.dev, c.stream,
+                               [W](uint32_t o) { return (o + W - 1) % W; }, [W](uint32_t n) { return (n + 1) % W; });
+}
+
+ncclResult_t rs_run(const Call& c) {
+    dcclComm* comm = c.comm;
+    const uint32_t W = comm->world;
+    switch (path_of(c)) {
+    case Path::kLocal: return stage_input(c.recv, c.send, c.count, c.dtype, c.form, c.dev, c.stream);
+    case Path::kDirect:
+        return direct_reduce_scatter(comm, c.send, c.recv, c.count, c.dtype, c.op, c.stream, c.form);
+    case Path::kHostDirect: return direct_reduce_scatter_host(comm, c.send, c.recv, c.count, c.dtype, c.op);
+    case Path::kWideStaged: return wide_staged(c);
+    case Path::kGrouped:  // slot r, reduced straight from sendbuff: no work copy
+        return reduce_scatter_grouped(comm, c.send, c.recv, c.count * W, c.dtype, c.op, c.stream, 0);
+    case Path::kRabenseifner:
+    case Path::kRing: break;
     }
-    return copy_bytes(recvbuff, static_cast<unsigned char*>(work) + size_t(r) * slot, slot, dev, stream);
+    const size_t slot = c.count * size_of_dtype(c.dtype);
+    ncclResult_t rc = ensure_work(comm, slot * W, c.dev);
+    if (rc != ncclSuccess) return rc;
+    void* work = c.dev ? comm->dev_work : comm->host_work;
+    rc = stage_input(work, c.send, c.count * W, c.dtype, c.form, c.dev, c.stream);  // dccl.cpp:585-609
+    if (rc == ncclSuccess) rc = ring_to_own_slot(c, work, c.count * W);
+    if (rc != ncclSuccess) return rc;
+    return copy_bytes(c.recv, static_cast<unsigned char*>(work) + size_t(comm->rank) * slot, slot, c.dev, c.stream);
 }
 
 ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
-                             ncclRedOp_t user_op, int root, ncclComm_t comm, Call* c, bool* todo) {
+                             ncclRedOp_t user_op, int root, ncclComm_t comm, Call* c) {
     validate_comm(comm, "ncclReduce");
-    *todo = false;
     c->user_op = c->op = user_op;
     ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
@@ -627,37 +576,30 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
     if ((rc = check_buffers(comm, sendbuff, iamroot ? recvbuff : sendbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduce, comm, sendbuff, recvbuff, count, datatype);
     c->root = root;
-    *todo = true;
     return ncclSuccess;
 }
 
-ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
-    const ncclComm_t comm = c.comm;
-    const void* sendbuff = c.send;
-    void* recvbuff = c.recv;
-    const size_t count = c.count;
-    const int datatype = c.dtype, op = c.op, root = c.root;
-    const SumForm& form = c.form;
-    const bool dev = c.dev;
+ncclResult_t reduce_run(const Call& c) {
+    dcclComm* comm = c.comm;
+    const uint32_t W = comm->world, r = comm->rank, root = uint32_t(c.root);
+    const bool iamroot = r == root, dev = c.dev;
+    hipStream_t stream = c.stream;
+    switch (path_of(c)) {
+    case Path::kLocal: return stage_input(c.recv, c.send, c.count, c.dtype, c.form, dev, stream);
+    case Path::kDirect:
+        return direct_reduce(comm, c.send, c.recv, c.count, c.dtype, c.op, root, stream, c.form);
+    case Path::kWideStaged: return wide_staged(c);
+    default: break;  // the ring, then the gather
+    }
     ncclResult_t rc;
-    const uint32_t W = comm->world, r = comm->rank;
-    const bool iamroot = r == uint32_t(root);
-    if (W > 1 && dev && direct_selected(comm))
-        return direct_reduce(comm, sendbuff, recvbuff, count, datatype, op, uint32_t(root), stream, form);
-    if (form.wide()) return wide_staged(c, stream);
-    const size_t total = count * size_of_dtype(datatype), slot = total / W;
-    void* rbuf = recvbuff;
+    const size_t total = c.count * size_of_dtype(c.dtype), slot = total / W;
+    void* rbuf = c.recv;
     if (!iamroot) {
         if ((rc = ensure_work(comm, total, dev)) != ncclSuccess) return rc;
         rbuf = dev ? comm->dev_work : comm->host_work;
     }
-    if ((rc = stage_input(rbuf, sendbuff, count, datatype, form, dev, stream)) != ncclSuccess) return rc;
-    if (W == 1) return ncclSuccess;
-    void* scratch = nullptr;
-    if ((rc = ring_scratch(comm, slot, dev, &scratch)) != ncclSuccess) return rc;
-    rc = reduce_scatter_ring(comm, rbuf, scratch, count, datatype, op, dev, stream,
-                             [W](uint32_t o) { return (o + W - 1) % W; }, [W](uint32_t n) { return (n + 1) % W; });
-    if (rc != ncclSuccess) return rc;
+    if ((rc = stage_input(rbuf, c.send, c.count, c.dtype, c.form, dev, stream)) != ncclSuccess) return rc;
+    if ((rc = ring_to_own_slot(c, rbuf, c.count)) != ncclSuccess) return rc;
     auto at = [&](uint32_t i) { return static_cast<unsigned char*>(rbuf) + size_t(i) * slot; };
     if (comm->rccl != nullptr && iamroot) {  // gather to the root (dccl.cpp:803-840): one RCCL group
         std::vector<void*> bufs(W);
@@ -666,9 +608,9 @@ ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
     }
     if (comm->p2p != nullptr) {  // gather to the root (dccl.cpp:803-840), one exchange per peer
         for (uint32_t p = 0; p < W && rc == ncclSuccess; ++p) {
-            if (p == uint32_t(root) || (!iamroot && p != r)) continue;
+            if (p == root || (!iamroot && p != r)) continue;
             rc = iamroot ? p2p_exchange(comm, nullptr, 0, 0, at(p), slot, p, stream)
-                         : p2p_exchange(comm, at(r), slot, uint32_t(root), nullptr, 0, 0, stream);
+                         : p2p_exchange(comm, at(r), slot, root, nullptr, 0, 0, stream);
         }
         return rc;
     }
@@ -677,14 +619,13 @@ ncclResult_t reduce_run(const Call& c, hipStream_t stream) {
             if (p != r && (rc = xport_recv(comm, p, at(p), slot, dev, stream)) != ncclSuccess) return rc;
         return ncclSuccess;
     }
-    if ((rc = xport_send(comm, uint32_t(root), at(r), slot, dev, stream)) != ncclSuccess) return rc;
-    return xport_wait_send(comm, uint32_t(root), dev, stream);
+    if ((rc = xport_send(comm, root, at(r), slot, dev, stream)) != ncclSuccess) return rc;
+    return xport_wait_send(comm, root, dev, stream);
 }
 
 ncclResult_t ag_validate(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
-                         ncclComm_t comm, Call* c, bool* todo) {
+                         ncclComm_t comm, Call* c) {
     validate_comm(comm, "ncclAllGather");
-    *todo = false;
     const size_t esz = size_of_dtype(datatype);
     if (esz == 0) return ncclInvalidArgument;
     if (sendcount == 0) return ncclSuccess;
@@ -692,26 +633,27 @@ ncclResult_t ag_validate(const void* sendbuff, void* recvbuff, size_t sendcount,
     const ncclResult_t rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev);
     if (rc != ncclSuccess) return rc;
     set_call(c, group::kAllGather, comm, sendbuff, recvbuff, sendcount, datatype);
-    *todo = true;
     return ncclSuccess;
 }
 
-ncclResult_t ag_run(const Call& c, hipStream_t stream) {
-    const ncclComm_t comm = c.comm;
-    const size_t esz = size_of_dtype(c.dtype);
-    if (comm->world > 1 && c.dev && direct_selected(comm))
-        return direct_all_gather(comm, c.send, c.recv, c.count, c.dtype, stream);
-    void* slot = static_cast<unsigned char*>(c.recv) + c.count * comm->rank * esz;
-    ncclResult_t rc;
-    if ((rc = copy_bytes(slot, c.send, c.count * esz, c.dev, stream)) != ncclSuccess) return rc;
+ncclResult_t ag_run(const Call& c) {
+    dcclComm* comm = c.comm;
+    const size_t bytes = c.count * size_of_dtype(c.dtype);
+    switch (path_of(c)) {
+    case Path::kLocal: return copy_bytes(c.recv, c.send, bytes, c.dev, c.stream);
+    case Path::kDirect: return direct_all_gather(comm, c.send, c.recv, c.count, c.dtype, c.stream);
+    default: break;  // the ring
+    }
+    void* slot = static_cast<unsigned char*>(c.recv) + bytes * comm->rank;
+    const ncclResult_t rc = copy_bytes(slot, c.send, bytes, c.dev, c.stream);
+    if (rc != ncclSuccess) return rc;
     const RankMap id = [](uint32_t x) { return x; };
-    return all_gather_ring(comm, c.recv, c.count, c.dtype, c.dev, stream, id, id);
+    return all_gather_ring(comm, c.recv, c.count, c.dtype, c.dev, c.stream, id, id);
 }
 
 ncclResult_t bcast_validate(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
-                            ncclComm_t comm, Call* c, bool* todo) {
+                            ncclComm_t comm, Call* c) {
     validate_comm(comm, "ncclBroadcast");
-    *todo = false;
     const size_t esz = size_of_dtype(datatype);
     const uint32_t W = comm->world, r = comm->rank;
     if (esz == 0 || root < 0 || uint32_t(root) >= W) return ncclInvalidArgument;
@@ -720,51 +662,50 @@ ncclResult_t bcast_validate(const void* sendbuff, void* recvbuff, size_t count, 
     if (rc != ncclSuccess) return rc;
     set_call(c, group::kBroadcast, comm, sendbuff, recvbuff, count, datatype);
     c->root = root;
-    *todo = true;
     return ncclSuccess;
 }
 
-ncclResult_t bcast_run(const Call& c, hipStream_t stream) {
-    const ncclComm_t comm = c.comm;
-    const void* sendbuff = c.send;
-    void* recvbuff = c.recv;
-    const size_t count = c.count;
-    const int datatype = c.dtype, root = c.root;
+ncclResult_t bcast_run(const Call& c) {
+    dcclComm* comm = c.comm;
+    const uint32_t W = comm->world, r = comm->rank, root = uint32_t(c.root);
     const bool dev = c.dev;
-    const uint32_t W = comm->world, r = comm->rank;
-    const size_t bytes = count * size_of_dtype(datatype);
+    hipStream_t stream = c.stream;
+    const size_t bytes = c.count * size_of_dtype(c.dtype);
+    switch (path_of(c)) {
+    case Path::kLocal: return copy_bytes(c.recv, c.send, bytes, dev, stream);
+    case Path::kDirect: return direct_broadcast(comm, c.send, c.recv, c.count, c.dtype, root, stream);
+    default: break;  // the root's fan-out
+    }
     ncclResult_t rc = ncclSuccess;
-    if (W > 1 && dev && direct_selected(comm))
-        return direct_broadcast(comm, sendbuff, recvbuff, count, datatype, uint32_t(root), stream);
     if (comm->p2p != nullptr) {  // root -> every rank, one exchange per peer (RCCL: one group)
-        if (r != uint32_t(root)) return p2p_exchange(comm, nullptr, 0, 0, recvbuff, bytes, uint32_t(root), stream);
+        if (r != root) return p2p_exchange(comm, nullptr, 0, 0, c.recv, bytes, root, stream);
         if (comm->rccl != nullptr) {
-            std::vector<void*> bufs(W, const_cast<void*>(sendbuff));
+            std::vector<void*> bufs(W, const_cast<void*>(c.send));
             rc = static_cast<ncclResult_t>(rccl_fan(comm->rccl, true, bufs.data(), bytes, W, r, stream));
-            return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
+            return rc == ncclSuccess ? copy_bytes(c.recv, c.send, bytes, dev, stream) : rc;
         }
         for (uint32_t p = 0; p < W && rc == ncclSuccess; ++p)
-            if (p != r) rc = p2p_exchange(comm, sendbuff, bytes, p, nullptr, 0, 0, stream);
-        return rc == ncclSuccess ? copy_bytes(recvbuff, sendbuff, bytes, dev, stream) : rc;
+            if (p != r) rc = p2p_exchange(comm, c.send, bytes, p, nullptr, 0, 0, stream);
+        return rc == ncclSuccess ? copy_bytes(c.recv, c.send, bytes, dev, stream) : rc;
     }
-    if (r == uint32_t(root)) {
+    if (r == root) {
         for (uint32_t p = 0; p < W; ++p)
-            if (p != r && (rc = xport_send(comm, p, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
-        if ((rc = copy_bytes(recvbuff, sendbuff, bytes, dev, stream)) != ncclSuccess) return rc;
+            if (p != r && (rc = xport_send(comm, p, c.send, bytes, dev, stream)) != ncclSuccess) return rc;
+        if ((rc = copy_bytes(c.recv, c.send, bytes, dev, stream)) != ncclSuccess) return rc;
         for (uint32_t p = 0; p < W; ++p)
             if (p != r && (rc = xport_wait_send(comm, p, dev, stream)) != ncclSuccess) return rc;
         return ncclSuccess;
     }
-    return xport_recv(comm, uint32_t(root), recvbuff, bytes, dev, stream);
+    return xport_recv(comm, root, c.recv, bytes, dev, stream);
 }
 
 ncclResult_t run_plain(const Call& c) {
     switch (c.api) {
-    case group::kAllReduce: return ar_run(c, c.stream);
-    case group::kReduceScatter: return rs_run(c, c.stream);
-    case group::kReduce: return reduce_run(c, c.stream);
-    case group::kAllGather: return ag_run(c, c.stream);
-    default: return bcast_run(c, c.stream);
+    case group::kAllReduce: return ar_run(c);
+    case group::kReduceScatter: return rs_run(c);
+    case group::kReduce: return reduce_run(c);
+    case group::kAllGather: return ag_run(c);
+    default: return bcast_run(c);
     }
 }
 
@@ -775,7 +716,8 @@ ncclResult_t run_plain(const Call& c) {
 // reduce_run grow that one underneath.  W == 1: the input's bytes.  A scaled wide sum (kWideScaledSum, one fp32)
 // takes the same route with dccl_local_convert_scaled as the narrowing pass, which multiplies as it rounds; the
 // fp32 collective in the middle never sees the scalar.  Its W == 1 is that pass from 16 bits to 16 bits.
-ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
+ncclResult_t wide_staged(const Call& c) {
+    hipStream_t stream = c.stream;
     dcclComm* comm = c.comm;
     const uint32_t W = comm->world;
     const bool rs = c.api == group::kReduceScatter;
@@ -797,8 +739,7 @@ ncclResult_t wide_staged(const Call& c, hipStream_t stream) {
     f.recv = rs ? wide + in_count : wide;
     f.dtype = ncclFloat32;
     f.op = ncclSum;
-    f.form = SumForm{};
-    f.stream = stream;
+    f.form = SumForm{};  // the builtin kind: path_of(f) is the fp32 collective these settings select
     rc = run_plain(f);
     if (rc != ncclSuccess || !has_out) return rc;
     if (scaled)
@@ -830,10 +771,13 @@ size_t coalesce_max_bytes() {
     return group::kDefaultMaxBytes;
 }
 
-// Inside a group: a validated call joins the queue.  Its SumForm holds a host-immediate scalar by value, so nothing
+// What every public collective does with its validator's answer: nothing more for an error or an empty call; else
+// the call runs, or inside a group joins the queue.  Its SumForm holds a host-immediate scalar by value, so nothing
 // refers to the op's slot later: the op may be destroyed, and its slot taken again, before the group ends.
-ncclResult_t enqueue(Call c, hipStream_t stream) {
+ncclResult_t submit(ncclResult_t rc, Call& c, hipStream_t stream) {
+    if (rc != ncclSuccess || c.comm == nullptr) return rc;
     c.stream = stream;
+    if (tl_depth == 0) return run_plain(c);
     tl_queue.push_back(c);
     g_group_stats[1].fetch_add(1, std::memory_order_relaxed);
     return ncclSuccess;
@@ -868,7 +812,12 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     dcclComm* comm = c0.comm;
     const uint32_t W = comm->world;
     const size_t esz = size_of_dtype(c0.dtype);
-    const size_t P = group::slots_of(W, runs_rabenseifner(c0));
+    // The slots of the algorithm that runs, asked of the selector; a wide run is cut like the fp32 collective that
+    // wide_staged runs inside it.
+    Call inner = c0;
+    inner.form = SumForm{};
+    const Path path = path_of(c0);
+    const size_t P = slots(path == Path::kWideStaged ? path_of(inner) : path, W);
     const group::Layout L = group::pack_layout(plan, n, P);
     const bool rs = c0.api == group::kReduceScatter;
     const size_t bytes = P * L.S + (rs ? L.S : 0);
@@ -897,7 +846,6 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     pc.send = pack;
     pc.recv = rs ? pack + P * L.S : pack;
     pc.count = rs ? L.S / esz : L.count;
-    pc.stream = st;
     const ncclResult_t crc = run_plain(pc);
     keep_first(&first, crc);
     g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
@@ -992,28 +940,22 @@ ncclResult_t ncclGroupEnd() {
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
     Call c;
-    bool todo = false;
-    const ncclResult_t rc = ar_validate(sendbuff, recvbuff, count, datatype, user_op, comm, &c, &todo);
-    if (rc != ncclSuccess || !todo) return rc;
-    return tl_depth > 0 ? enqueue(c, stream) : ar_run(c, stream);
+    const ncclResult_t rc = ar_validate(sendbuff, recvbuff, count, datatype, user_op, comm, &c);
+    return submit(rc, c, stream);
 }
 
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, ncclDataType_t datatype,
                                ncclRedOp_t user_op, ncclComm_t comm, hipStream_t stream) {
     Call c;
-    bool todo = false;
-    const ncclResult_t rc = rs_validate(sendbuff, recvbuff, recvcount, datatype, user_op, comm, &c, &todo);
-    if (rc != ncclSuccess || !todo) return rc;
-    return tl_depth > 0 ? enqueue(c, stream) : rs_run(c, stream);
+    const ncclResult_t rc = rs_validate(sendbuff, recvbuff, recvcount, datatype, user_op, comm, &c);
+    return submit(rc, c, stream);
 }
 
 ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                         ncclRedOp_t user_op, int root, ncclComm_t comm, hipStream_t stream) {
     Call c;
-    bool todo = false;
-    const ncclResult_t rc = reduce_validate(sendbuff, recvbuff, count, datatype, user_op, root, comm, &c, &todo);
-    if (rc != ncclSuccess || !todo) return rc;
-    return tl_depth > 0 ? enqueue(c, stream) : reduce_run(c, stream);
+    const ncclResult_t rc = reduce_validate(sendbuff, recvbuff, count, datatype, user_op, root, comm, &c);
+    return submit(rc, c, stream);
 }
 
 ncclResult_t ncclRedOpCreatePreMulSum(ncclRedOp_t* op, void* scalar, ncclDataType_t datatype,
@@ -1053,19 +995,15 @@ ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
 ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype,
                            ncclComm_t comm, hipStream_t stream) {
     Call c;
-    bool todo = false;
-    const ncclResult_t rc = ag_validate(sendbuff, recvbuff, sendcount, datatype, comm, &c, &todo);
-    if (rc != ncclSuccess || !todo) return rc;
-    return tl_depth > 0 ? enqueue(c, stream) : ag_run(c, stream);
+    const ncclResult_t rc = ag_validate(sendbuff, recvbuff, sendcount, datatype, comm, &c);
+    return submit(rc, c, stream);
 }
 
 ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
                            ncclComm_t comm, hipStream_t stream) {
     Call c;
-    bool todo = false;
-    const ncclResult_t rc = bcast_validate(sendbuff, recvbuff, count, datatype, root, comm, &c, &todo);
-    if (rc != ncclSuccess || !todo) return rc;
-    return tl_depth > 0 ? enqueue(c, stream) : bcast_run(c, stream);
+    const ncclResult_t rc = bcast_validate(sendbuff, recvbuff, count, datatype, root, comm, &c);
+    return submit(rc, c, stream);
 }
 
 ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,

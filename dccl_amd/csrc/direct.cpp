@@ -857,19 +857,6 @@ int ipc_stats(uint64_t* out, int n) {
     return int(sizeof(v) / sizeof(v[0]));
 }
 
-// In-process groups take the direct collectives for device buffers unless DCCL_ALLREDUCE_ALGORITHM names
-// another algorithm: "direct", "auto" and unset select them.  They are faster than the ring at every
-// size measured and give the ring's results bit for bit.  Host buffers, the RCCL
-// transport and groups above 8 ranks keep the ring.
-bool direct_selected(const dcclComm* c) {
-    if (c->ipc != nullptr) return true;
-    if (c->p2p != nullptr || c->world > kDirectMaxWorld) return false;
-    const char* a = std::getenv("DCCL_ALLREDUCE_ALGORITHM");
-    if (a == nullptr || *a == 0) return true;
-    const std::string s(a);
-    return s == "auto" || s == "direct";
-}
-
 // ncclAllReduce: the ring all-reduce (all_reduce_ring.cpp:8-79) leaves chunk r+1 reduced on rank r;
 // here rank r reduces that chunk from every rank's input in the ring's order, then pulls every other
 // chunk from the rank that reduced it.  On the IPC transport `send` is read from the scratch copy, and
@@ -904,14 +891,17 @@ ncclResult_t direct_all_reduce(dcclComm* c, const void* send, void* recv, size_t
     return arrive(c, st, copy_pairs(src, dst, slot, st), &P);  // peers are done reading our buffers
 }
 
-bool host_direct_selected(const dcclComm* c, size_t slot_bytes) {
-    (void)slot_bytes;  // any size: dccl_local_reduce_chain_host stages in pieces
-    if (c->ipc != nullptr || c->p2p != nullptr || c->group == nullptr || c->world > kDirectMaxWorld) return false;
-    const char* a = std::getenv("DCCL_ALLREDUCE_ALGORITHM");
-    if (a == nullptr || *a == 0) return true;
-    const std::string s(a);
-    return s == "auto" || s == "direct";
+namespace {
+// chain() on the host buffers an in-process group published: the same operands, one staged launch of any size
+// (dccl_local_reduce_chain_host stages in pieces).
+ncclResult_t chain_host(const Group& g, uint32_t W, uint32_t first, size_t off, const void* own, void* dst,
+                        size_t elems, int dtype, int op, uint32_t rank) {
+    if (fault_injected("direct_combine", rank)) return dccl::ncclUnhandledCudaError;
+    const void* sends[kDirectMaxWorld];
+    for (uint32_t j = 0; j + 1 < W; ++j) sends[j] = static_cast<const unsigned char*>(g.pub_in[(first + j) % W]) + off;
+    return static_cast<ncclResult_t>(dccl_local_reduce_chain_host(sends, int(W - 1), own, dst, dtype, elems, op));
 }
+}  // namespace
 
 // The same choreography as direct_all_reduce on host memory: rank r reduces chunk r+1 from every rank's
 // input in the ring's order with one staged chain kernel (one GPU round trip instead of the ring's W-1),
@@ -926,14 +916,9 @@ ncclResult_t direct_all_reduce_host(dcclComm* c, const void* send, void* recv, s
     g.pub_out[r] = recv;
     g.barrier();  // every rank's buffers are published and its inputs are final
     const uint32_t mine = (r + 1) % W;
-    const void* sends[kDirectMaxWorld];
-    for (uint32_t j = 0; j + 1 < W; ++j)
-        sends[j] = static_cast<const unsigned char*>(g.pub_in[(mine + j) % W]) + mine * slot;
-    const ncclResult_t rc = fault_injected("direct_combine", r)
-                                ? dccl::ncclUnhandledCudaError
-                                : static_cast<ncclResult_t>(dccl_local_reduce_chain_host(
-                                      sends, int(W - 1), static_cast<const unsigned char*>(send) + mine * slot,
-                                      static_cast<unsigned char*>(recv) + mine * slot, dtype, slot_elems, op));
+    const ncclResult_t rc =
+        chain_host(g, W, mine, mine * slot, static_cast<const unsigned char*>(send) + mine * slot,
+                   static_cast<unsigned char*>(recv) + mine * slot, slot_elems, dtype, op, r);
     const bool all = g.barrier(rc == dccl::ncclSuccess);  // every chunk reduced by its owner
     if (all)
         for (uint32_t k = 0; k < W; ++k)
@@ -954,14 +939,8 @@ ncclResult_t direct_reduce_scatter_host(dcclComm* c, const void* send, void* rec
     g.pub_in[r] = send;
     g.pub_out[r] = recv;
     g.barrier();
-    const void* sends[kDirectMaxWorld];
-    for (uint32_t j = 0; j + 1 < W; ++j)
-        sends[j] = static_cast<const unsigned char*>(g.pub_in[(r + 1 + j) % W]) + r * slot;
-    const ncclResult_t rc = fault_injected("direct_combine", r)
-                                ? dccl::ncclUnhandledCudaError
-                                : static_cast<ncclResult_t>(dccl_local_reduce_chain_host(
-                                      sends, int(W - 1), static_cast<const unsigned char*>(send) + r * slot, recv,
-                                      dtype, recvcount, op));
+    const ncclResult_t rc = chain_host(g, W, (r + 1) % W, r * slot, static_cast<const unsigned char*>(send) + r * slot,
+                                       recv, recvcount, dtype, op, r);
     const bool all = g.barrier(rc == dccl::ncclSuccess);  // peers are done reading our input
     return rc != dccl::ncclSuccess ? rc : (all ? dccl::ncclSuccess : dccl::ncclRemoteError);
 }

@@ -29,8 +29,6 @@
 
 namespace dccl_amd {
 
-constexpr uint32_t kDirectMaxWorld = 8;  // one 8-GPU node; <= 8 copy pairs / chain sends per launch
-
 // Cross-process IPC transport: join (rank 0 creates the segment and publishes its name through a
 // file in DCCL_BOOTSTRAP_DIR keyed by DCCL_BOOTSTRAP_TAG / MASTER_PORT) and leave.
 ncclResult_t ipc_join(dccl::dcclComm* c, uint32_t world, uint32_t rank);
@@ -43,11 +41,7 @@ ncclResult_t ipc_deregister(void* buffer);
 // returns how many there are.
 int ipc_stats(uint64_t* out, int n);
 
-// True when the collectives of `c` on device buffers take the direct algorithms: always on the
-// IPC transport; on the in-process transport (W <= 8) unless DCCL_ALLREDUCE_ALGORITHM is ring or
-// rabenseifner.
-bool direct_selected(const dccl::dcclComm* c);
-
+// When a collective takes these: select.hpp (W <= kDirectMaxWorld, defined there).
 // `form` (here and in direct_reduce_scatter / direct_reduce): which sum the chain launch computes (comm.hpp SumForm;
 // op is ncclSum for every kind but kBuiltin).  kPremulSum multiplies every contribution by the scalar as it reads it;
 // kWideSum (fp16 / bf16) accumulates in fp32 and rounds once, the bytes moved unchanged; kWideScaledSum multiplies that
@@ -57,8 +51,7 @@ ncclResult_t direct_all_reduce(dccl::dcclComm* c, const void* send, void* recv, 
 
 // Host buffers of an in-process group: the direct all_reduce with the chain combine staged through the
 // GPU (dccl_local_reduce_chain_host, staged in double-buffered pieces) and the all-gather by memcpy from
-// the owners' buffers.  Selected like direct_selected().
-bool host_direct_selected(const dccl::dcclComm* c, size_t slot_bytes);
+// the owners' buffers.
 ncclResult_t direct_all_reduce_host(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype,
                                     int op);
 ncclResult_t direct_reduce_scatter_host(dccl::dcclComm* c, const void* send, void* recv, size_t recvcount,

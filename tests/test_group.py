@@ -731,6 +731,40 @@ def test_packed_run_keeps_its_scalar(gpu, monkeypatch):
             assert out[r][i].tobytes() == want[i][r].tobytes(), (r, i)
 
 
+@pytest.mark.gpu
+def test_queued_call_runs_by_the_name_it_was_validated_under(gpu, monkeypatch):
+    """W = 3 thread ranks queue one fp32 Sum all-reduce of 4 elements under DCCL_ALLREDUCE_ALGORITHM=rabenseifner:
+    4 is a multiple of 2^floor(log2 3) = 2, the count that name is checked for, and not of W.  Once every rank has
+    queued it, one rank sets the variable to "" and only then does any rank reach group_end.  The call runs the
+    algorithm it was validated under: every rank holds the Rabenseifner result, bit for bit, not a direct all-reduce
+    with slots of 4 / 3 = 1 element."""
+    import torch
+    import dccl_amd as d
+    monkeypatch.setenv("DCCL_ALLREDUCE_ALGORITHM", "rabenseifner")
+    W, n = 3, 4
+    inputs = [np.random.default_rng(90 + r).standard_normal(n).astype(np.float32) for r in range(W)]
+    want = rabsim.rabenseifner_allreduce([x.copy() for x in inputs], combine_of(7, SUM))
+    meet = threading.Barrier(W)
+
+    def body(comm, r):
+        stream = torch.cuda.Stream()
+        t = torch.from_numpy(inputs[r].copy()).cuda()
+        torch.cuda.synchronize()
+        assert d.group_start() == 0
+        assert comm.all_reduce(t.data_ptr(), t.data_ptr(), n, 7, SUM, stream.cuda_stream) == 0
+        meet.wait(timeout=60)
+        if r == 0:
+            os.environ["DCCL_ALLREDUCE_ALGORITHM"] = ""
+        meet.wait(timeout=60)
+        assert d.group_end() == 0
+        stream.synchronize()
+        return t.cpu().numpy()
+
+    out = run_ranks(W, body)
+    for r in range(W):
+        assert out[r].tobytes() == want[r].tobytes(), (r, out[r], want[r])
+
+
 def _ipc_group_rank(r, W, counts, tag, q):
     os.environ["DCCL_BOOTSTRAP_TAG"] = tag
     os.environ.setdefault("DCCL_IPC_TIMEOUT_S", "60")
