@@ -116,6 +116,8 @@ def _load():
         "dccl_local_reduce_chain_wide_scaled": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                         c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_local_convert_scaled": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
+        "dccl_local_reduce_chain_widen": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
+                                                  c_size_t, c_int, c_void_p]),
         "dccl_register_host_memory": (c_int, [c_void_p, c_size_t]),
         "dccl_deregister_host_memory": (c_int, [c_void_p]),
         "dccl_size_of_type": (c_size_t, [c_int]),
@@ -143,6 +145,7 @@ def _load():
         "dccl_red_op_destroy": (c_int, [c_int, c_void_p]),
         "dccl_red_op_create_wide_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_void_p]),
         "dccl_red_op_create_wide_scaled_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
+        "dccl_red_op_create_widened_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_int, c_void_p]),
         "dccl_rccl_available": (c_int, []),
         "dccl_bootstrap_unique_id": (c_int, [ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
         "dccl_bootstrap_done": (c_int, [ctypes.c_uint32, ctypes.c_uint32]),
@@ -180,6 +183,7 @@ EXPORTED_SYMBOLS = [
     "dccl_copy_rows_multi", "dccl_copy_rows_check", "dccl_group_start", "dccl_group_end", "dccl_group_stats",
     "dccl_local_reduce_chain_wide", "dccl_local_convert", "dccl_red_op_create_wide_sum",
     "dccl_local_reduce_chain_wide_scaled", "dccl_local_convert_scaled", "dccl_red_op_create_wide_scaled_sum",
+    "dccl_local_reduce_chain_widen", "dccl_red_op_create_widened_sum",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -300,6 +304,15 @@ def local_reduce_chain_wide_scaled(send_ptrs, own_ptr: int, dst_ptr: int, dtype:
     arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
     return int(lib.dccl_local_reduce_chain_wide_scaled(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
                                                        scalar_ptr, int(residence), stream or None))
+
+
+def local_reduce_chain_widen(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, accumulate: int,
+                             stream: int = 0) -> int:
+    """local_reduce_chain_wide's fp32 accumulator stored as float32 (``dst_ptr`` addresses ``count`` float32), or with
+    ``accumulate`` 1 added to what dst holds by one more fp32 add; dst shares no byte with any operand."""
+    arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
+    return int(lib.dccl_local_reduce_chain_widen(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
+                                                 int(accumulate), stream or None))
 
 
 def local_convert_scaled(src_ptr: int, src_dtype: int, dst_ptr: int, dst_dtype: int, count: int, scalar_ptr: int,
@@ -463,6 +476,15 @@ class Comm:
         op = ctypes.c_int(-1)
         rc = int(lib.dccl_red_op_create_wide_scaled_sum(ctypes.byref(op), scalar_ptr, int(dtype), int(residence),
                                                         self.handle))
+        return rc, int(op.value)
+
+    def red_op_create_widened_sum(self, dtype: int, accumulate: int):
+        """dcclRedOpCreateWidenedSum: returns (rc, op); ``op`` sums fp16 / bf16 contributions in fp32 and delivers
+        float32: reduce_scatter / reduce of this communicator with ``dtype``, a 16-bit send buffer and a FLOAT32
+        receive buffer (device memory).  ``accumulate`` 1 adds the sum to the receive buffer's content, 0 replaces
+        it."""
+        op = ctypes.c_int(-1)
+        rc = int(lib.dccl_red_op_create_widened_sum(ctypes.byref(op), int(dtype), int(accumulate), self.handle))
         return rc, int(op.value)
 
     def red_op_destroy(self, op: int) -> int:

@@ -96,6 +96,9 @@ private:
 //   kPremulSum      ncclRedOpCreatePreMulSum: the scalar is one element of the operands' dtype, times every operand
 //   kWideSum        dcclRedOpCreateWideSum: fp16 / bf16 accumulated in fp32, rounded once; no scalar
 //   kWideScaledSum  dcclRedOpCreateWideScaledSum: the scalar is ONE fp32, times the finished fp32 accumulator
+//   kWidenedSum     dcclRedOpCreateWidenedSum: fp16 / bf16 accumulated in fp32 and NOT rounded: recvbuff holds fp32
+//                   (ncclReduceScatter and ncclReduce only); no scalar; `bits` holds its accumulate flag (0 / 1:
+//                   the sum replaces recvbuff's content, or is added to it by one fp32 add): accumulate()
 // Readers switch on `kind` or ask the accessor named for their question, never the scalar's storage.  A host-immediate
 // scalar lives in `bits`: a copy of the form (a queued call, a packed run) is complete, and its scalar() valid as long.
 // (SumKind itself is in select.hpp, which has no HIP include.)
@@ -105,6 +108,8 @@ struct SumForm {
     const void* dev_ptr = nullptr;  // ncclScalarDevice: read by each collective's kernels when they run
     bool wide() const { return kind == kWideSum || kind == kWideScaledSum; }
     bool has_scalar() const { return kind == kPremulSum || kind == kWideScaledSum; }
+    bool widened() const { return kind == kWidenedSum; }  // the output is fp32, whatever the input's dtype
+    bool accumulate() const { return kind == kWidenedSum && bits != 0; }
     // the C entry points' (scalar, residence) pair
     const void* scalar() const { return dev_ptr != nullptr ? dev_ptr : static_cast<const void*>(&bits); }
     int residence() const { return dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate; }

@@ -106,9 +106,17 @@ ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, co
     case kPremulSum:
         return static_cast<ncclResult_t>(dccl_local_scale(src, dst, dtype, count, form.scalar(), form.residence(), st));
     case kWideSum:
-    case kWideScaledSum: break;
+    case kWideScaledSum:
+    case kWidenedSum: break;
     }
     return dccl::ncclInternalError;
+}
+
+// [a, a + na) and [b, b + nb) share a byte: a widened sum's sendbuff (16-bit elements) against its fp32 recvbuff,
+// which have no in-place form.
+bool ranges_share_a_byte(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y ? y - x < na : x - y < nb;
 }
 
 ncclResult_t placement(const void* send, const void* recv, bool* device) {
@@ -472,6 +480,8 @@ ncclResult_t ar_validate(const void* sendbuff, void* recvbuff, size_t count, ncc
     c->user_op = c->op = user_op;
     ncclResult_t rc = resolve_op(comm, datatype, &c->op, &c->form);
     if (rc != ncclSuccess) return rc;
+    // no widened all-reduce: its all-gather half would move fp32 whatever the first half does
+    if (c->form.widened()) return ncclInvalidUsage;
     if (count == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
     if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
@@ -521,6 +531,9 @@ ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount,
     if (rc != ncclSuccess) return rc;
     if (recvcount == 0) return ncclSuccess;
     if (sendbuff == nullptr || recvbuff == nullptr) return ncclInvalidArgument;
+    if (c->form.widened() && ranges_share_a_byte(sendbuff, recvcount * comm->world * size_of_dtype(datatype), recvbuff,
+                                                 recvcount * sizeof(float)))
+        return ncclInvalidArgument;  // recvbuff holds fp32: no in-place form
     if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype);
     return ncclSuccess;
@@ -573,6 +586,9 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
     if (count % W) return ncclInvalidArgument;  // dccl.cpp:762-767
     const bool iamroot = r == uint32_t(root);
     if (sendbuff == nullptr || (iamroot && recvbuff == nullptr)) return ncclInvalidArgument;
+    if (c->form.widened() && iamroot &&
+        ranges_share_a_byte(sendbuff, count * size_of_dtype(datatype), recvbuff, count * sizeof(float)))
+        return ncclInvalidArgument;  // the root's recvbuff holds fp32: no in-place form
     if ((rc = check_buffers(comm, sendbuff, iamroot ? recvbuff : sendbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduce, comm, sendbuff, recvbuff, count, datatype);
     c->root = root;
@@ -709,6 +725,41 @@ ncclResult_t run_plain(const Call& c) {
     }
 }
 
+// A widened sum (dcclRedOpCreateWidenedSum) on every path but the direct ones, ncclReduceScatter and
+// ncclReduce only: recvbuff holds fp32.  The input is widened into the fp32 staging buffer and the ncclFloat32 /
+// ncclSum collective these settings select runs on it, as for a wide sum; nothing is rounded.  Without `accumulate`
+// that collective writes recvbuff itself (the root's, for ncclReduce: it is the buffer the fp32 ring then runs in).
+// With it the result stays in staging (a reduce-scatter's behind the widened input) and one fp32 Sum combine adds it
+// to recvbuff.  W == 1: the conversion alone, or the conversion into staging and the same add.
+ncclResult_t widened_staged(const Call& c) {
+    hipStream_t stream = c.stream;
+    dcclComm* comm = c.comm;
+    const uint32_t W = comm->world;
+    const bool rs = c.api == group::kReduceScatter, acc = c.form.accumulate();
+    const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
+    const bool has_out = rs || comm->rank == uint32_t(c.root);
+    if (W == 1 && !acc)
+        return static_cast<ncclResult_t>(dccl_local_convert(c.send, c.dtype, c.recv, ncclFloat32, out_count, stream));
+    ncclResult_t rc = ensure_wide(comm, (in_count + (rs && acc ? out_count : 0)) * sizeof(float));
+    if (rc != ncclSuccess) return rc;
+    float* wide = static_cast<float*>(comm->dev_wide);
+    rc = static_cast<ncclResult_t>(dccl_local_convert(c.send, c.dtype, wide, ncclFloat32, in_count, stream));
+    if (rc != ncclSuccess) return rc;
+    const float* sum = wide;  // W == 1: the widened input is the sum
+    if (W > 1) {
+        Call f = c;
+        f.send = wide;
+        f.recv = acc ? (rs ? wide + in_count : wide) : (has_out ? c.recv : static_cast<void*>(wide));
+        f.dtype = ncclFloat32;
+        f.op = ncclSum;
+        f.form = SumForm{};  // the builtin kind: path_of(f) is the fp32 collective these settings select
+        rc = run_plain(f);
+        sum = static_cast<const float*>(f.recv);
+    }
+    if (rc != ncclSuccess || !has_out || !acc) return rc;
+    return static_cast<ncclResult_t>(dccl_local_reduce(sum, c.recv, ncclFloat32, out_count, ncclSum, stream));
+}
+
 // A wide sum (dcclRedOpCreateWideSum) on every path but the direct ones: widen the input into the communicator's
 // fp32 staging buffer, run the ncclFloat32 / ncclSum collective these settings select on it (ring, Rabenseifner,
 // p2p, RCCL ring or grouped), and round its result once into recvbuff (ncclReduce: on the root only).  A
@@ -723,8 +774,9 @@ ncclResult_t wide_staged(const Call& c) {
     const bool rs = c.api == group::kReduceScatter;
     const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
     const bool has_out = c.api != group::kReduce || comm->rank == uint32_t(c.root);
-    const SumForm& form = c.form;  // kWideSum or kWideScaledSum: the callers test form.wide()
+    const SumForm& form = c.form;  // kWideSum, kWideScaledSum or kWidenedSum: what select() sends here
     const bool scaled = form.kind == kWideScaledSum;
+    if (form.widened()) return widened_staged(c);
     if (W == 1 && scaled)
         return static_cast<ncclResult_t>(dccl_local_convert_scaled(c.send, c.dtype, c.recv, c.dtype, out_count,
                                                                    form.scalar(), form.residence(), stream));
@@ -884,6 +936,7 @@ ncclResult_t run_queue(const std::vector<Call>& q) {
         plan[i].root = c.root;
         plan[i].device = c.dev;
         plan[i].world = W;
+        plan[i].never_packed = c.form.widened();  // 16-bit sendbuff, fp32 recvbuff: the pack assumes one element size
     }
     ncclResult_t first = ncclSuccess;
     for (const group::Run& r : group::plan_runs(plan.data(), plan.size(), coalesce_max_bytes())) {
@@ -982,6 +1035,16 @@ ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, n
     if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
     // always one fp32, whatever the datatype
     return create_user_op(comm, kWideScaledSum, datatype, scalar, residence, sizeof(float), op);
+}
+
+ncclResult_t dcclRedOpCreateWidenedSum(ncclRedOp_t* op, ncclDataType_t datatype, int accumulate, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    if (op == nullptr) return ncclInvalidArgument;
+    if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
+    if (accumulate != 0 && accumulate != 1) return ncclInvalidArgument;
+    // no scalar: the form's `bits` carry the flag (comm.hpp SumForm::accumulate)
+    const uint64_t flag = uint64_t(accumulate);
+    return create_user_op(comm, kWidenedSum, datatype, &flag, ncclScalarHostImmediate, sizeof(flag), op);
 }
 
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
@@ -1169,6 +1232,13 @@ extern "C" int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, i
         return dccl::dcclRedOpCreateWideScaledSum(h, scalar, static_cast<dccl::ncclDataType_t>(dtype),
                                                   static_cast<dccl::ncclScalarResidence_t>(residence),
                                                   static_cast<dccl::ncclComm_t>(comm));
+    });
+}
+
+extern "C" int dccl_red_op_create_widened_sum(int* op, int dtype, int accumulate, void* comm) {
+    return create_handle(op, [&](dccl::ncclRedOp_t* h) {
+        return dccl::dcclRedOpCreateWidenedSum(h, static_cast<dccl::ncclDataType_t>(dtype), accumulate,
+                                               static_cast<dccl::ncclComm_t>(comm));
     });
 }
 

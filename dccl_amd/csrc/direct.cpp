@@ -643,6 +643,9 @@ ncclResult_t chain(const Peers& P, uint32_t W, uint32_t first, size_t off, const
     case kWideScaledSum:  // the fp32 accumulator times one fp32 scalar before that rounding
         rc = dccl_local_reduce_chain_wide_scaled(sends, k, own, dst, dtype, elems, form.scalar(), form.residence(), s);
         break;
+    case kWidenedSum:  // that accumulator stored as fp32 (dst holds fp32), or added to what dst holds
+        rc = dccl_local_reduce_chain_widen(sends, k, own, dst, dtype, elems, form.accumulate() ? 1 : 0, s);
+        break;
     }
     return static_cast<ncclResult_t>(rc);
 }
@@ -971,6 +974,8 @@ ncclResult_t direct_reduce(dcclComm* c, const void* send, void* recv, size_t cou
     const uint32_t W = c->world, r = c->rank;
     if (W > kDirectMaxWorld) return dccl::ncclInvalidUsage;
     const size_t slot_elems = count / W, slot = slot_elems * size_of_dtype(dtype);
+    // the root's output slots: of `dtype`, but fp32 for a widened sum (recv holds fp32)
+    const size_t out_slot = form.widened() ? slot_elems * sizeof(float) : slot;
     Publish pub;
     pub.in = send;
     pub.in_bytes = slot * W;
@@ -980,7 +985,7 @@ ncclResult_t direct_reduce(dcclComm* c, const void* send, void* recv, size_t cou
     if (!met) return rc;
     if (r == root)
         for (uint32_t o = 0; o < W && rc == dccl::ncclSuccess; ++o)
-            rc = chain(P, W, (o + 1) % W, o * slot, P.in[o] + o * slot, static_cast<unsigned char*>(recv) + o * slot,
+            rc = chain(P, W, (o + 1) % W, o * slot, P.in[o] + o * slot, static_cast<unsigned char*>(recv) + o * out_slot,
                        slot_elems, dtype, op, st, r, form);
     return arrive(c, st, rc, &P);
 }

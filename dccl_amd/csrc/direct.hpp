@@ -45,7 +45,8 @@ int ipc_stats(uint64_t* out, int n);
 // `form` (here and in direct_reduce_scatter / direct_reduce): which sum the chain launch computes (comm.hpp SumForm;
 // op is ncclSum for every kind but kBuiltin).  kPremulSum multiplies every contribution by the scalar as it reads it;
 // kWideSum (fp16 / bf16) accumulates in fp32 and rounds once, the bytes moved unchanged; kWideScaledSum multiplies that
-// accumulator by its one fp32 scalar before the rounding.
+// accumulator by its one fp32 scalar before the rounding.  kWidenedSum (direct_reduce_scatter / direct_reduce only)
+// stores that accumulator as fp32, or adds it to what is there: `recv` then holds fp32 elements.
 ncclResult_t direct_all_reduce(dccl::dcclComm* c, const void* send, void* recv, size_t count, int dtype, int op,
                                hipStream_t st, const SumForm& form);
 

@@ -43,6 +43,9 @@ struct Call {
     int root = 0;
     bool device = false;
     uint32_t world = 1;
+    // A call whose two buffers differ in element size (a widened sum: 16-bit sendbuff, fp32 recvbuff) is never
+    // packed: the pack and its layout assume one `esz`.  It runs alone, in issue order.
+    bool never_packed = false;
 };
 
 struct Run {
@@ -51,7 +54,8 @@ struct Run {
 };
 
 inline bool packable(const Call& c, size_t max_bytes) {
-    return max_bytes > 0 && c.api <= kReduce && c.device && c.world > 1 && c.count > 0 && c.count * c.esz < max_bytes;
+    return max_bytes > 0 && !c.never_packed && c.api <= kReduce && c.device && c.world > 1 && c.count > 0 &&
+           c.count * c.esz < max_bytes;
 }
 
 inline bool same_run(const Call& a, const Call& b) {

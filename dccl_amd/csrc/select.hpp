@@ -13,8 +13,9 @@ namespace dccl_amd {
 
 constexpr uint32_t kDirectMaxWorld = 8;  // one 8-GPU node; <= 8 copy pairs / chain sends per launch
 
-// Which sum a reduction computes (comm.hpp SumForm carries it with its scalar).
-enum SumKind : int { kBuiltin = 0, kPremulSum, kWideSum, kWideScaledSum };
+// Which sum a reduction computes (comm.hpp SumForm carries it with its scalar).  New kinds are appended: the values
+// are what tests/test_select.py and the selector's callers pass.
+enum SumKind : int { kBuiltin = 0, kPremulSum, kWideSum, kWideScaledSum, kWidenedSum };
 
 // DCCL_ALLREDUCE_ALGORITHM (the reference's DCCL/allreduce_algorithm key, dccl.hpp:38-46, whose values are "ring"
 // and "rabenseifner": DCCL_ALLREDUCE_RING / DCCL_ALLREDUCE_RABENSEIFNER of include/dccl/dccl.hpp).  Unset, "" and
@@ -45,7 +46,8 @@ enum class Path {
     kLocal,         // W == 1: dst = src (times the scalar of a pre-multiplied sum)
     kDirect,        // direct.hpp: every rank reads its peers' device buffers
     kHostDirect,    // the same choreography on host buffers of an in-process group
-    kWideStaged,    // a wide sum off the direct path: widened, run as an fp32 collective, rounded once
+    kWideStaged,    // a wide sum off the direct path: widened, run as an fp32 collective, rounded once (a widened
+                    // sum: not rounded)
     kGrouped,       // algorithms.hpp: grouped exchanges on RCCL
     kRabenseifner,  // ncclAllReduce only
     kRing,          // the ring; for ncclReduce the ring and its gather, for ncclBroadcast the root's fan-out
@@ -56,7 +58,8 @@ enum class Path {
 // RCCL or a plugged-in transport, where "direct" runs the ring.  "grouped" is not the default on RCCL yet (§7.2).
 inline Path select(int api, Transport t, uint32_t world, bool device, SumKind kind, AlgoName name) {
     const bool reduces = api <= group::kReduce;
-    const bool wide = reduces && (kind == kWideSum || kind == kWideScaledSum);
+    // a widened sum (fp32 recvbuff) goes where the wide sums go: direct, else staged through fp32
+    const bool wide = reduces && (kind == kWideSum || kind == kWideScaledSum || kind == kWidenedSum);
     if (world == 1) return wide ? Path::kWideStaged : Path::kLocal;
     const bool peer_read = t == Transport::kThreads && world <= kDirectMaxWorld &&
                            (name == AlgoName::kAuto || name == AlgoName::kDirect);

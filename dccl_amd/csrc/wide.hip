@@ -5,6 +5,7 @@
 //   dccl_local_reduce_chain_wide          acc = widen(sends[0][i]); acc = widen(sends[j][i]) + acc, j = 1..k-1;
 //                                         acc = widen(own[i]) + acc;  dst[i] = round16(acc)
 //   dccl_local_reduce_chain_wide_scaled   the same acc;  dst[i] = round16(acc * s)
+//   dccl_local_reduce_chain_widen         the same acc;  dst (fp32)[i] = acc, or dst[i] + acc
 //   dccl_local_convert                    dst[i] = widen(src[i]) (fp16 / bf16 -> fp32, exact) or round16(src[i])
 //                                         (fp32 -> fp16 / bf16, nearest-even)
 //   dccl_local_convert_scaled             dst[i] = round16(as_fp32(src[i]) * s), src fp32 or dst's own 16-bit type
@@ -174,6 +175,72 @@ __global__ __launch_bounds__(kBlock) void wide_scaled_chain_elem_kernel(SendList
                                                  WideScaledChain<T>{{load_scalar<float>(sa)}});
 }
 
+// ---- widened chain (dccl_local_reduce_chain_widen): the wide chain's accumulator stored as fp32,
+// ACC: added to what dst holds by one more fp32 add after the chain (prior + acc; two adds, nothing to contract).
+// A sibling of chain_vec_body, whose loads, order and edge elements it follows: the 16-bit operands are walked in
+// 16-B vectors, dst in the 2 x 16 B that hold the same eight elements (convert_vec_kernel<T, true>'s stores).
+// `head` elements bring the 16-bit operands to their 16-B boundary; dst is on one there too (widen_typed). ----
+template <typename T, int K, bool ACC, typename C>
+__global__ __launch_bounds__(C::BLOCK) void widen_chain_vec_kernel(SendList sends, const unsigned char* own,
+                                                                   unsigned char* dst, size_t head, size_t nvec,
+                                                                   size_t tail) {
+    static_assert(C::UNROLL == 1, "one vector per lane");
+    const size_t off = head * sizeof(T);
+    const u32x4* vo = reinterpret_cast<const u32x4*>(own + off);
+    u32x4* vd = reinterpret_cast<u32x4*>(dst + head * sizeof(float));
+    const size_t ntiles = (nvec + C::TILE - 1) / C::TILE;
+    for (size_t t = C::XCD ? xcd_remap(blockIdx.x, gridDim.x) : run_tile<C::RUN>(blockIdx.x, gridDim.x); t < ntiles;
+         t += gridDim.x) {
+        const size_t i = t * C::TILE + threadIdx.x;
+        if (i < nvec) {
+            U32x4x2 prior{};
+            if constexpr (ACC) prior = U32x4x2{{ld16<true>(vd + 2 * i), ld16<true>(vd + 2 * i + 1)}};
+            u32x4 s[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                s[k] = ld16<(C::POLICY & kNtSend) != 0>(reinterpret_cast<const u32x4*>(sends.p[k] + off) + i);
+            const u32x4 o = ld16<true>(vo + i);
+            F32x8 acc = widen16<T>(s[0]);
+#pragma unroll
+            for (int k = 1; k < K; ++k) acc = add16<T>(s[k], acc);
+            acc = add16<T>(o, acc);
+            if constexpr (ACC) {
+                const F32x8 was = __builtin_bit_cast(F32x8, prior);
+#pragma unroll
+                for (int l = 0; l < kLanes16; ++l) acc.f[l] = was.f[l] + acc.f[l];
+            }
+            const U32x4x2 w = __builtin_bit_cast(U32x4x2, acc);
+            __builtin_nontemporal_store(w.v[0], vd + 2 * i);
+            __builtin_nontemporal_store(w.v[1], vd + 2 * i + 1);
+        }
+    }
+    if (blockIdx.x == 0) {
+        for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x) {
+            const size_t i = edge_index<T>(j, head, nvec);
+            float acc = Wide<T>::widen(ld_elem<T, true>(sends.p[0], i));
+#pragma unroll
+            for (int k = 1; k < K; ++k) acc = Wide<T>::widen(ld_elem<T, true>(sends.p[k], i)) + acc;
+            acc = Wide<T>::widen(ld_elem<T, true>(own, i)) + acc;
+            if constexpr (ACC) acc = ld_elem<float, true>(dst, i) + acc;
+            st_elem<float, true>(dst, i, acc);
+        }
+    }
+}
+
+// Any placement, one element per thread and step (correctness only).  ALIGNED: the 16-bit operands on 2-byte and
+// dst on 4-byte boundaries; else byte loads and stores on every side.
+template <typename T, bool ACC, bool ALIGNED>
+__global__ __launch_bounds__(kBlock) void widen_chain_elem_kernel(SendList sends, int nsend, const unsigned char* own,
+                                                                  unsigned char* dst, size_t count) {
+    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < count; i += size_t(gridDim.x) * kBlock) {
+        float acc = Wide<T>::widen(ld_elem<T, ALIGNED>(sends.p[0], i));
+        for (int k = 1; k < nsend; ++k) acc = Wide<T>::widen(ld_elem<T, ALIGNED>(sends.p[k], i)) + acc;
+        acc = Wide<T>::widen(ld_elem<T, ALIGNED>(own, i)) + acc;
+        if constexpr (ACC) acc = ld_elem<float, ALIGNED>(dst, i) + acc;
+        st_elem<float, ALIGNED>(dst, i, acc);
+    }
+}
+
 // ---- convert: `half` is the 16-bit side, `full` the fp32 side; WIDEN: half -> full, else full -> half ----
 template <typename T, bool WIDEN>
 __global__ __launch_bounds__(64) void convert_vec_kernel(const unsigned char* src, unsigned char* dst, size_t head,
@@ -308,6 +375,41 @@ int convert_scaled_typed(const void* src, void* dst, size_t count, ScalarArg sa,
     return launch(reinterpret_cast<const void*>(&convert_scaled_vec_kernel<T, S>), grid_for(sp, 64), args, stream, 64);
 }
 
+// The widened chain's placement rule and launch.  The vector kernel needs every 16-bit operand element-aligned and
+// at one 16-B phase, dst on a 4-byte boundary, and dst on a 16-B boundary past the head elements that bring the
+// 16-bit operands to theirs (place_pass, `own` leading; no further head elements towards dst's 128-B lines).  It
+// launches like launch_chain_form, under the plain chain's caps selected by the fp32 bytes written, which nobody
+// has measured for this kernel (more registers per lane, 4 or 8 more bytes per element on the destination side).
+// Any other placement takes the element-wise kernel: correctness only, nobody has tuned it.
+template <typename T, bool ACC>
+int widen_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count, hipStream_t stream) {
+    const uintptr_t ao = reinterpret_cast<uintptr_t>(own), ad = reinterpret_cast<uintptr_t>(dst);
+    bool elem_ok = ao % sizeof(T) == 0 && ad % sizeof(float) == 0, in_phase = true;
+    for (int k = 0; k < nsend; ++k) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(sends[k]);
+        if (a % sizeof(T)) elem_ok = false;
+        if ((a ^ ao) & 15) in_phase = false;
+    }
+    SendList sl = send_list(sends, nsend);
+    auto o = static_cast<const unsigned char*>(own);
+    auto d = static_cast<unsigned char*>(dst);
+    PassPlacement p{false, false, {0, 0, 0}};
+    if (elem_ok && in_phase) p = place_pass(ao, sizeof(T), ad, sizeof(float), count);
+    if (!p.vec_ok) {
+        void* args[] = {&sl, &nsend, &o, &d, &count};
+        const void* fn = elem_ok ? reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, true>)
+                                 : reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, false>);
+        return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
+    }
+    Split& sp = p.sp;
+    void* args[] = {&sl, &o, &d, &sp.head, &sp.nvec, &sp.tail};
+    return with_k<1, 8>(nsend, [&](auto K) {
+        return launch(reinterpret_cast<const void*>(&widen_chain_vec_kernel<T, K.value, ACC, DefaultCfg>),
+                      grid_for(sp, DefaultCfg::TILE), args, stream, DefaultCfg::BLOCK,
+                      caps::lds(caps::kChain, K.value, caps_bytes(count * sizeof(float))));
+    });
+}
+
 bool is_16bit_float(int dtype) { return dtype == kFloat16 || dtype == kBfloat16; }
 
 // [a, a + na) and [b, b + nb) share a byte
@@ -329,6 +431,28 @@ extern "C" int dccl_local_reduce_chain_wide(const void* const* sends, int nsend,
     hipStream_t st = static_cast<hipStream_t>(stream);
     return dtype == kFloat16 ? launch_chain_form<WideChainKernels, f16_bits>(sends, nsend, own, dst, count, st)
                              : launch_chain_form<WideChainKernels, bf16_bits>(sends, nsend, own, dst, count, st);
+}
+
+extern "C" int dccl_local_reduce_chain_widen(const void* const* sends, int nsend, const void* own, void* dst,
+                                             int dtype, size_t count, int accumulate, void* stream) {
+    if (!is_16bit_float(dtype)) return DCCL_INVALID_ARGUMENT;
+    if (accumulate != 0 && accumulate != 1) return DCCL_INVALID_ARGUMENT;
+    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
+    if (count == 0) return DCCL_SUCCESS;
+    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
+    for (int k = 0; k < nsend; ++k)
+        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
+    // no shared byte with the fp32 destination (dccl_local_convert's rule: the element sizes differ)
+    const size_t in_bytes = count * size_of_dtype(dtype), out_bytes = count * sizeof(float);
+    for (int k = 0; k < nsend; ++k)
+        if (ranges_intersect(sends[k], in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    if (ranges_intersect(own, in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == kFloat16)
+        return accumulate ? widen_typed<f16_bits, true>(sends, nsend, own, dst, count, st)
+                          : widen_typed<f16_bits, false>(sends, nsend, own, dst, count, st);
+    return accumulate ? widen_typed<bf16_bits, true>(sends, nsend, own, dst, count, st)
+                      : widen_typed<bf16_bits, false>(sends, nsend, own, dst, count, st);
 }
 
 extern "C" int dccl_local_convert(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count,

@@ -134,6 +134,24 @@ ncclResult_t dcclRedOpCreateWideSum(ncclRedOp_t* op, ncclDataType_t datatype, nc
 ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, ncclDataType_t datatype,
                                           ncclScalarResidence_t residence, ncclComm_t comm);
 
+/** Widened sum: the wide sum's fp32 accumulator is not rounded but delivered as fp32, for the caller that keeps an
+ *  fp32 gradient shard: main_grad32[i] (+)= sum over ranks of widen(grad16_r[i]).  ncclReduceScatter and ncclReduce
+ *  accept the handle on `comm` with `datatype` (ncclFloat16 or ncclBfloat16 only) and device buffers: `sendbuff`
+ *  holds `datatype` elements, `recvbuff` holds FP32 elements (`recvcount` / `count` of them; ncclReduce: on the root
+ *  only).  The result is the bits of widening every rank's input to fp32, running the ncclFloat32 / ncclSum
+ *  collective this communicator and these settings would run and, with `accumulate` == 1, adding that result to the
+ *  previous content of `recvbuff` with one fp32 add (`accumulate` == 0: it replaces the content).  The handle comes
+ *  from the same table as the other user ops (ncclNumOps + slot, 16 live ops per communicator together;
+ *  ncclRedOpDestroy releases it).  The direct collectives fuse everything into their one chain launch and read
+ *  16-bit bytes from the peers; every other path stages through an fp32 buffer of the communicator.  Inside
+ *  ncclGroupStart / ncclGroupEnd such a call runs in issue order and is never packed.  NULL `op`, another datatype
+ *  or an `accumulate` other than 0 / 1: ncclInvalidArgument; a 17th live op: ncclInvalidUsage.  At the collective:
+ *  ncclAllReduce with the handle: ncclInvalidUsage (there is no widened all-reduce); another datatype:
+ *  ncclInvalidArgument; host buffers: ncclInvalidUsage; `sendbuff` and `recvbuff` sharing any byte:
+ *  ncclInvalidArgument (the element sizes differ: no in-place form).  There is no scalar: an fp32 consumer applies
+ *  1/W itself. */
+ncclResult_t dcclRedOpCreateWidenedSum(ncclRedOp_t* op, ncclDataType_t datatype, int accumulate, ncclComm_t comm);
+
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,

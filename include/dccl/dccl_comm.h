@@ -111,6 +111,14 @@
  *                         the same scalar on every rank.  Create: NULL op or scalar, a residence other than 0 / 1
  *                         or a dtype other than 6 / 9 -> 4; a 17th live op -> 5.  The direct collectives fuse the
  *                         multiply into their chain launch, the staged paths into their narrowing pass.
+ *   dccl_red_op_create_widened_sum  dcclRedOpCreateWidenedSum: the wide sum's fp32 accumulator delivered as fp32
+ *                         instead of rounded.  dccl_reduce_scatter and dccl_reduce only (dccl_all_reduce 5): `send`
+ *                         holds dtype 6 / 9 elements, `recv` holds FP32 (recvcount / count of them, on the root only
+ *                         for dccl_reduce); accumulate 1 adds the sum to recv's previous content with one fp32 add,
+ *                         0 replaces it.  Same table and handles as the other ops.  Create: NULL op, a dtype other
+ *                         than 6 / 9 or an accumulate other than 0 / 1 -> 4; a 17th live op -> 5.  At the
+ *                         collective: another dtype 4; send and recv sharing any byte 4; host buffers 5.  Inside a
+ *                         group the call is never packed.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -143,6 +151,7 @@ int dccl_red_op_create_premul_sum(int* op, const void* scalar, int dtype, int re
 int dccl_red_op_destroy(int op, void* comm);
 int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm);
 int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
+int dccl_red_op_create_widened_sum(int* op, int dtype, int accumulate, void* comm);
 int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);

@@ -158,6 +158,26 @@ int dccl_local_convert_scaled(const void* src, int src_dtype, void* dst, int dst
                               const void* scalar, int residence, void* stream);
 
 /*
+ * Widened sum (the device half of dcclRedOpCreateWidenedSum, include/dccl/dccl.hpp): the wide sum's fp32 accumulator
+ * is not rounded at all but stored as fp32, optionally added to what dst holds.
+ *   dccl_local_reduce_chain_widen   sends[j] and own hold `count` elements of dtype 6 (fp16) or 9 (bf16), dst holds
+ *                                   `count` fp32.  acc is dccl_local_reduce_chain_wide's, unchanged: acc =
+ *                                   widen(sends[0][i]); acc = widen(sends[j][i]) + acc for j = 1..nsend-1; acc =
+ *                                   widen(own[i]) + acc.  accumulate == 0: dst[i] = acc.  accumulate == 1: dst[i] =
+ *                                   dst[i] + acc, one more IEEE fp32 add applied after the chain (never folded into
+ *                                   the chain as a first operand, never contracted).
+ * fp32 and fp16 denormals are kept; NaN payloads are unpinned.
+ * Validation, in this order: dtype not 6 / 9 4, unknown dtypes included; accumulate not 0 / 1 4; nsend outside 1..8
+ * or NULL sends 4; count == 0 succeeds; NULL operand 4; a source or own sharing ANY byte with [dst, dst + 4 count)
+ * 4 (the element sizes differ, so there is no in-place form: dccl_local_convert's rule); launch failure 1.
+ * The 16-byte vector kernel runs when every 16-bit operand is 2-byte aligned, all of them share one 16-byte phase
+ * p, dst is 4-byte aligned and dst + 4 h is on a 16-byte boundary, h = ((16 - p) % 16) / 2 being the head elements
+ * that bring the 16-bit operands to theirs.  Any other placement takes an element-wise kernel kept for correctness.
+ */
+int dccl_local_reduce_chain_widen(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
+                                  size_t count, int accumulate, void* stream);
+
+/*
  * Multi-source device copy: dsts[y][0..bytes) = srcs[y][0..bytes) for y < npairs (<= 8), in one
  * launch, so the reads of several peers' chunks use several xGMI links at once (the all-gather
  * half of the direct collectives; replaces W-1 ring all-gather steps,

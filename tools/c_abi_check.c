@@ -117,6 +117,18 @@ static void cpu_checks(void) {
     CHECK(dccl_local_convert_scaled(c + 1, 9, c, 9, 4, &half, 1, NULL) == DCCL_INVALID_ARGUMENT); /* partial overlap */
     CHECK(dccl_red_op_create_wide_scaled_sum(&wide_op, &half, 9, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null comm */
     CHECK(dccl_red_op_create_wide_scaled_sum(&wide_op, &half, 9, 2, NULL) == DCCL_INVALID_ARGUMENT);
+    /* widened sum: dtype, accumulate, nsend, count 0, NULL operands, any shared byte with the fp32 dst, in that order */
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, a, b, 7, 4, 0, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, a, b, 10, 4, 2, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, a, b, 9, 0, 2, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(sends, 9, a, b, 9, 4, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(NULL, 1, a, b, 6, 0, 0, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, NULL, NULL, 9, 0, 1, NULL) == DCCL_SUCCESS);
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, NULL, b, 9, 4, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_local_reduce_chain_widen(sends, 1, c, c, 9, 4, 0, NULL) == DCCL_INVALID_ARGUMENT); /* no in-place form */
+    /* a source 4 bytes past dst: behind the end of two 16-bit elements, inside two fp32 ones */
+    CHECK(dccl_local_reduce_chain_widen(ov, 1, a, c, 6, 2, 1, NULL) == DCCL_INVALID_ARGUMENT);
+    CHECK(dccl_red_op_create_widened_sum(&wide_op, 9, 1, NULL) == DCCL_INVALID_ARGUMENT); /* null communicator */
     /* batched row copy: every validation case answers before any device work (never-dereferenced addresses) */
     {
         char* const base = (char*)(uintptr_t)0x100000000000ull;
