@@ -107,6 +107,7 @@ def _load():
         "dccl_copy_multi": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_size_t, c_void_p]),
         "dccl_copy_rows_multi": (c_int, [ctypes.POINTER(dccl_copy_rows_t), c_int, ctypes.c_uint32, c_void_p]),
         "dccl_copy_rows_check": (c_int, [ctypes.POINTER(dccl_copy_rows_t), c_int, ctypes.c_uint32]),
+        "dccl_add_rows_f32_multi": (c_int, [ctypes.POINTER(dccl_copy_rows_t), c_int, ctypes.c_uint32, c_void_p]),
         "dccl_local_scale": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_local_reduce_chain_premul": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                    c_size_t, c_void_p, c_int, c_void_p]),
@@ -183,7 +184,7 @@ EXPORTED_SYMBOLS = [
     "dccl_copy_rows_multi", "dccl_copy_rows_check", "dccl_group_start", "dccl_group_end", "dccl_group_stats",
     "dccl_local_reduce_chain_wide", "dccl_local_convert", "dccl_red_op_create_wide_sum",
     "dccl_local_reduce_chain_wide_scaled", "dccl_local_convert_scaled", "dccl_red_op_create_wide_scaled_sum",
-    "dccl_local_reduce_chain_widen", "dccl_red_op_create_widened_sum",
+    "dccl_local_reduce_chain_widen", "dccl_red_op_create_widened_sum", "dccl_add_rows_f32_multi",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -353,6 +354,12 @@ def copy_rows_multi(segs, rows: int, stream: int = 0) -> int:
 def copy_rows_check(segs, rows: int) -> int:
     """The validation of copy_rows_multi alone (0 or 4); launches nothing."""
     return int(lib.dccl_copy_rows_check(_rows_array(segs), len(segs), int(rows)))
+
+
+def add_rows_f32_multi(segs, rows: int, stream: int = 0) -> int:
+    """Batched strided fp32 row accumulate, one launch: ``segs`` as for copy_rows_multi, every row_bytes a multiple
+    of 4; element e of row r of every segment becomes dst + src by one fp32 add."""
+    return int(lib.dccl_add_rows_f32_multi(_rows_array(segs), len(segs), int(rows), stream or None))
 
 
 def host_reduce_gpu_min_bytes(dtype: int) -> int:

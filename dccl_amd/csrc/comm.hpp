@@ -206,6 +206,8 @@ ncclResult_t ensure_wide(dccl::dcclComm* c, size_t bytes);  // device memory
 
 // dccl_copy_rows_multi's launch without its validation (copy_rows.hip), for plans disjoint by construction.
 int copy_rows_launch(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, hipStream_t stream);
+// dccl_add_rows_f32_multi's, likewise (add_rows.hip): every row_bytes a multiple of 4.
+int add_rows_launch(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, hipStream_t stream);
 
 // Test-only fault injection: DCCL_FAULT_INJECT=<site>:<rank> makes `site` fail on that rank, so the
 // tests can check that one rank's failure reaches every member of the group (as an error) instead of

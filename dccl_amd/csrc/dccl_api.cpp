@@ -872,7 +872,12 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     const size_t P = slots(path == Path::kWideStaged ? path_of(inner) : path, W);
     const group::Layout L = group::pack_layout(plan, n, P);
     const bool rs = c0.api == group::kReduceScatter;
-    const size_t bytes = P * L.S + (rs ? L.S : 0);
+    // A widened run (16-bit in, fp32 out) is the widened collective on library-owned buffers: its
+    // fp32 result goes to an output region behind the packed input, one slot of it for a reduce-scatter, all P for a
+    // reduce.  A plain reduce-scatter has such a region already; a plain reduce runs in place.
+    const bool widened = c0.form.widened();
+    const size_t out_at = rs || widened ? P * L.S : 0;
+    const size_t bytes = P * L.S + (rs ? L.S_out : widened ? P * L.S_out : 0);
     hipStream_t st = c0.stream;
     const size_t had = comm->dev_pack_bytes;
     ncclResult_t rc = ensure_pack(comm, bytes);
@@ -896,8 +901,9 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     keep_first(&first, static_cast<ncclResult_t>(copy_rows_launch(segs, int(n), uint32_t(P), st)));
     Call pc = c0;
     pc.send = pack;
-    pc.recv = rs ? pack + P * L.S : pack;
+    pc.recv = pack + out_at;
     pc.count = rs ? L.S / esz : L.count;
+    if (widened) pc.form.bits = 0;  // accumulate cleared: the region receives the accumulator itself, the unpack adds
     const ncclResult_t crc = run_plain(pc);
     keep_first(&first, crc);
     g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
@@ -908,10 +914,11 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     g_group_stats[5].fetch_add(packed, std::memory_order_relaxed);
     if (crc == ncclSuccess && (c0.api != group::kReduce || comm->rank == uint32_t(c0.root))) {
         for (size_t i = 0; i < n; ++i) {
-            if (rs) segs[i] = {pack + P * L.S + L.off[i], calls[i].recv, L.slot[i], 0, 0};
-            else segs[i] = {pack + L.off[i], calls[i].recv, L.slot[i], L.S, L.slot[i]};
+            if (rs) segs[i] = {pack + out_at + L.out_off[i], calls[i].recv, L.out_slot[i], 0, 0};
+            else segs[i] = {pack + out_at + L.out_off[i], calls[i].recv, L.out_slot[i], L.S_out, L.out_slot[i]};
         }
-        keep_first(&first, static_cast<ncclResult_t>(copy_rows_launch(segs, int(n), rs ? 1u : uint32_t(P), st)));
+        const auto unpack = c0.form.accumulate() ? add_rows_launch : copy_rows_launch;  // recvbuff += or = the result
+        keep_first(&first, static_cast<ncclResult_t>(unpack(segs, int(n), rs ? 1u : uint32_t(P), st)));
     }
     for (hipStream_t o : others) keep_first(&first, stream_join(comm, st, o));
     if (comm->dev_pack_done == nullptr)
@@ -936,7 +943,7 @@ ncclResult_t run_queue(const std::vector<Call>& q) {
         plan[i].root = c.root;
         plan[i].device = c.dev;
         plan[i].world = W;
-        plan[i].never_packed = c.form.widened();  // 16-bit sendbuff, fp32 recvbuff: the pack assumes one element size
+        if (c.form.widened()) plan[i].out_esz = sizeof(float);  // 16-bit sendbuff, fp32 recvbuff
     }
     ncclResult_t first = ncclSuccess;
     for (const group::Run& r : group::plan_runs(plan.data(), plan.size(), coalesce_max_bytes())) {

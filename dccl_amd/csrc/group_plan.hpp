@@ -27,7 +27,9 @@ constexpr size_t kMaxRun = 32;        // tensors per coalesced run (dccl_copy_ro
 constexpr size_t kSlotAlign = 128;    // kDeviceCachelineSize: every packed slot starts on a line
 // Tensors of this many bytes or more are never packed: the largest of 4 KiB, 64 KiB, 1 MiB, 16 MiB and 64 MiB at
 // which a coalesced group of 16 was still at least 10 % faster than its plain calls (5.5 x at 1 MiB, 0.85 x at
-// 16 MiB; one MI355X, thread ranks, W = 4).
+// 16 MiB; one MI355X, thread ranks, W = 4).  It serves widened runs too, compared against their
+// 16-bit bytes: packing them was still 1.5 x faster at 4 MiB, the largest of 4 KiB .. 16 MiB with a gain of 10 % or
+// more, so they need no lower limit of their own (§7.11).
 constexpr size_t kDefaultMaxBytes = size_t(1) << 20;
 
 // What the plan may look at of one queued call.  `count` is the element count of the whole reduced buffer
@@ -43,9 +45,11 @@ struct Call {
     int root = 0;
     bool device = false;
     uint32_t world = 1;
-    // A call whose two buffers differ in element size (a widened sum: 16-bit sendbuff, fp32 recvbuff) is never
-    // packed: the pack and its layout assume one `esz`.  It runs alone, in issue order.
+    // Set: the call runs alone, in issue order, whatever else holds.
     bool never_packed = false;
+    // Element size of the call's OUTPUT where it differs from `esz` (a widened sum: 16-bit sendbuff, fp32 recvbuff:
+    // 4); 0: the same as `esz`.  Calls of one run agree on it: the op value decides it, and same_run compares that.
+    size_t out_esz = 0;
 };
 
 struct Run {
@@ -78,9 +82,17 @@ inline std::vector<Run> plan_runs(const Call* calls, size_t n, size_t max_bytes)
 
 // Packed layout of a run of n <= kMaxRun tensors cut into P slots: tensor i's slot k lies at byte
 // k * S + off[i] of the packed buffer, slot[i] bytes long; pad bytes sit at the end of each packed slot only.
+//
+// The collective's result lies in an output region of its own elements, out_esz bytes each (esz unless the run's
+// calls say otherwise): element j of the packed input is element j of the output, so tensor i's slot k lies at
+// byte k * S_out + out_off[i] of the region, out_slot[i] bytes long, each the input's number times out_esz / esz.
+// With equal sizes the two layouts are one.  16-bit in, fp32 out: every output offset is a multiple of 4 and every
+// output slot k * S_out starts on a 256-B boundary of the region.
 struct Layout {
     size_t slot[kMaxRun], off[kMaxRun];
+    size_t out_slot[kMaxRun], out_off[kMaxRun];
     size_t S = 0;      // bytes of one packed slot, a multiple of kSlotAlign
+    size_t S_out = 0;  // bytes of one slot of the output region
     size_t count = 0;  // elements of the packed buffer: P * S / esz
 };
 
@@ -94,6 +106,12 @@ inline Layout pack_layout(const Call* calls, size_t n, size_t P) {
     }
     L.S = (sum + kSlotAlign - 1) / kSlotAlign * kSlotAlign;
     L.count = P * L.S / calls[0].esz;
+    const size_t esz = calls[0].esz, out_esz = calls[0].out_esz != 0 ? calls[0].out_esz : esz;
+    for (size_t i = 0; i < n; ++i) {
+        L.out_slot[i] = L.slot[i] / esz * out_esz;
+        L.out_off[i] = L.off[i] / esz * out_esz;
+    }
+    L.S_out = L.S / esz * out_esz;
     return L;
 }
 

@@ -144,7 +144,9 @@ ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, n
  *  from the same table as the other user ops (ncclNumOps + slot, 16 live ops per communicator together;
  *  ncclRedOpDestroy releases it).  The direct collectives fuse everything into their one chain launch and read
  *  16-bit bytes from the peers; every other path stages through an fp32 buffer of the communicator.  Inside
- *  ncclGroupStart / ncclGroupEnd such a call runs in issue order and is never packed.  NULL `op`, another datatype
+ *  ncclGroupStart / ncclGroupEnd consecutive calls with the SAME handle are coalesced like other reductions (below;
+ *  the limit is on the 16-bit payload), with the separate calls' bits; calls with different handles, or a widened
+ *  and a plain or wide call, never share a run.  NULL `op`, another datatype
  *  or an `accumulate` other than 0 / 1: ncclInvalidArgument; a 17th live op: ncclInvalidUsage.  At the collective:
  *  ncclAllReduce with the handle: ncclInvalidUsage (there is no widened all-reduce); another datatype:
  *  ncclInvalidArgument; host buffers: ncclInvalidUsage; `sendbuff` and `recvbuff` sharing any byte:

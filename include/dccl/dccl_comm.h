@@ -118,7 +118,10 @@
  *                         0 replaces it.  Same table and handles as the other ops.  Create: NULL op, a dtype other
  *                         than 6 / 9 or an accumulate other than 0 / 1 -> 4; a 17th live op -> 5.  At the
  *                         collective: another dtype 4; send and recv sharing any byte 4; host buffers 5.  Inside a
- *                         group the call is never packed.
+ *                         group consecutive calls with the same handle are coalesced like other reductions (the
+ *                         limit is on the 16-bit payload; an accumulate handle's run is unpacked by
+ *                         dccl_add_rows_f32_multi); calls with different handles, or a widened and a plain or wide
+ *                         call, never share a run.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_

@@ -213,6 +213,22 @@ int dccl_copy_rows_multi(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows,
 int dccl_copy_rows_check(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows);
 
 /*
+ * Batched strided fp32 row accumulate, one launch: for every segment i < nsegs (<= 32), every row r < rows and
+ * every element e < row_bytes / 4,
+ *     dst[r * dst_stride + 4 e] = dst[r * dst_stride + 4 e] + src[r * src_stride + 4 e]      (fp32)
+ * one IEEE fp32 add per element, round to nearest even, denormals kept; the payload of a NaN result is not pinned.
+ * It is the add dccl_local_reduce_chain_widen applies for accumulate == 1, and the unpack of a coalesced run of
+ * widened sums created with accumulate = 1: the segments are the ones dccl_copy_rows_multi would
+ * unpack by.  Bytes of dst between its rows are not touched; src is only read.  Either side may lie at any byte
+ * address: destination rows on a 4-byte boundary are walked in aligned 16-byte vectors with at most three head and
+ * three tail elements, a destination row off that boundary is combined element by element (correct, not fast).
+ * Validation, before any HIP call: dccl_copy_rows_check's rules in their order (dst is read as well as written,
+ * which "no destination byte is a source byte or another destination's byte" already covers; nsegs == 0
+ * succeeds), then a row_bytes that is not a multiple of 4 -> 4; launch failure 1.
+ */
+int dccl_add_rows_f32_multi(const dccl_copy_rows_t* segs, int nsegs, uint32_t rows, void* stream);
+
+/*
  * Host combine, synchronous: `send` and `recv` are host pointers (the RDMA
  * receive buffers of the reference's host path).  Replaces the reference's CPU
  * boundary do_host_reduce<DT>

@@ -148,6 +148,20 @@ static void cpu_checks(void) {
         seg[0].src = NULL;
         CHECK(dccl_copy_rows_multi(seg, 2, 1, NULL) == DCCL_INVALID_ARGUMENT);
     }
+    /* batched fp32 row accumulate: the row copy's rules, then row_bytes % 4 */
+    {
+        char* const base = (char*)(uintptr_t)0x100000000000ull;
+        dccl_copy_rows_t seg[2] = {{base, base + 4096, 100, 100, 256}, {base + 1024, base + 4096 + 100, 30, 32, 256}};
+        CHECK(dccl_add_rows_f32_multi(seg, 33, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_add_rows_f32_multi(NULL, 1, 4, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_add_rows_f32_multi(seg, 2, 0, NULL) == DCCL_INVALID_ARGUMENT);
+        CHECK(dccl_add_rows_f32_multi(NULL, 0, 4, NULL) == DCCL_SUCCESS);
+        CHECK(dccl_copy_rows_check(seg, 2, 4) == DCCL_SUCCESS);
+        CHECK(dccl_add_rows_f32_multi(seg, 2, 4, NULL) == DCCL_INVALID_ARGUMENT); /* 30 bytes: no whole fp32 */
+        seg[1].row_bytes = 28;
+        seg[1].dst = base + 4096 + 99; /* one shared byte */
+        CHECK(dccl_add_rows_f32_multi(seg, 2, 4, NULL) == DCCL_INVALID_ARGUMENT);
+    }
     /* group calls: depth per thread, an invalid call inside a group answers at once */
     {
         uint64_t st0[6] = {0}, st1[6] = {0};
