@@ -171,6 +171,9 @@ struct dccl::dcclComm {
     // fp32 reduce-scatter and non-root reduce that run ON it already use dev_work.
     void* dev_wide = nullptr;
     size_t dev_wide_bytes = 0;
+    // Recorded behind every call that used dev_scratch, dev_work or dev_wide: the next such call, maybe on another
+    // stream, waits for it before its first write to them (dccl_api.cpp run_call).
+    hipEvent_t dev_scratch_done = nullptr;
     dccl_amd::UserOp user_ops[dccl_amd::kMaxUserOps];  // used by the communicator's own thread only
 };
 

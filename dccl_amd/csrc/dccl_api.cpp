@@ -378,6 +378,7 @@ ncclResult_t ncclCommFinalize(ncclComm_t comm) {
     if (comm->dev_pack) (void)hipFree(comm->dev_pack);
     if (comm->dev_wide) (void)hipFree(comm->dev_wide);
     if (comm->dev_pack_done) (void)hipEventDestroy(comm->dev_pack_done);
+    if (comm->dev_scratch_done) (void)hipEventDestroy(comm->dev_scratch_done);
     if (comm->dev_pack_join) (void)hipEventDestroy(comm->dev_pack_join);
     for (void* h : {comm->host_scratch, comm->host_work}) {
         if (h) {
@@ -823,22 +824,61 @@ size_t coalesce_max_bytes() {
     return group::kDefaultMaxBytes;
 }
 
+ncclResult_t hip_rc(hipError_t e) {
+    if (e == hipSuccess) return ncclSuccess;
+    (void)hipGetLastError();
+    return ncclUnhandledCudaError;
+}
+
+inline void keep_first(ncclResult_t* first, ncclResult_t rc) {
+    if (*first == ncclSuccess) *first = rc;
+}
+
+// The call stages through dev_work, dev_scratch or dev_wide: buffers of the communicator that the next such call
+// writes again, maybe on another stream.  (dev_pack has its own guard, dev_pack_done in run_packed.)
+bool uses_library_scratch(const Call& c) {
+    if (!c.dev) return false;
+    switch (path_of(c)) {
+    case Path::kWideStaged:  // dev_wide, and whatever the fp32 collective inside it takes
+    case Path::kGrouped: return true;  // dev_scratch
+    case Path::kRabenseifner: return use_scratch();
+    case Path::kRing:  // ncclReduceScatter and a non-root ncclReduce run in dev_work; the scratchpad is an option
+        return c.api == group::kReduceScatter || c.api == group::kReduce || (c.api == group::kAllReduce && use_scratch());
+    case Path::kLocal:
+    case Path::kDirect:
+    case Path::kHostDirect: break;
+    }
+    return false;
+}
+
+// A collective as ncclGroupEnd or a plain call issues it.  Calls of one communicator may come on different streams
+// (INTEGRATION.md), and nothing else orders the library's own buffers between two of them: a call that uses them
+// waits, before its first write, for the event recorded behind the last call that did, and records it behind itself.
+// One stream: the wait is on an event of the same stream, and adds nothing to the order.  The collective runs
+// whatever the wait or the record answer: the peers are in it.
+ncclResult_t run_call(const Call& c) {
+    if (!uses_library_scratch(c)) return run_plain(c);
+    dcclComm* comm = c.comm;
+    ncclResult_t first = ncclSuccess;
+    if (comm->dev_scratch_done != nullptr)
+        keep_first(&first, hip_rc(hipStreamWaitEvent(c.stream, comm->dev_scratch_done, 0)));
+    else
+        keep_first(&first, hip_rc(hipEventCreateWithFlags(&comm->dev_scratch_done, hipEventDisableTiming)));
+    keep_first(&first, run_plain(c));
+    if (comm->dev_scratch_done != nullptr) keep_first(&first, hip_rc(hipEventRecord(comm->dev_scratch_done, c.stream)));
+    return first;
+}
+
 // What every public collective does with its validator's answer: nothing more for an error or an empty call; else
 // the call runs, or inside a group joins the queue.  Its SumForm holds a host-immediate scalar by value, so nothing
 // refers to the op's slot later: the op may be destroyed, and its slot taken again, before the group ends.
 ncclResult_t submit(ncclResult_t rc, Call& c, hipStream_t stream) {
     if (rc != ncclSuccess || c.comm == nullptr) return rc;
     c.stream = stream;
-    if (tl_depth == 0) return run_plain(c);
+    if (tl_depth == 0) return run_call(c);
     tl_queue.push_back(c);
     g_group_stats[1].fetch_add(1, std::memory_order_relaxed);
     return ncclSuccess;
-}
-
-ncclResult_t hip_rc(hipError_t e) {
-    if (e == hipSuccess) return ncclSuccess;
-    (void)hipGetLastError();
-    return ncclUnhandledCudaError;
 }
 
 // `to` waits for everything enqueued on `from` so far.  One event of the communicator serves every join: a wait
@@ -850,10 +890,6 @@ ncclResult_t stream_join(dcclComm* comm, hipStream_t from, hipStream_t to) {
     }
     const ncclResult_t rc = hip_rc(hipEventRecord(comm->dev_pack_join, from));
     return rc == ncclSuccess ? hip_rc(hipStreamWaitEvent(to, comm->dev_pack_join, 0)) : rc;
-}
-
-inline void keep_first(ncclResult_t* first, ncclResult_t rc) {
-    if (*first == ncclSuccess) *first = rc;
 }
 
 // One coalesced run (group_plan.hpp): pack -> the ordinary collective on the packed buffer -> unpack, on the
@@ -904,7 +940,7 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     pc.recv = pack + out_at;
     pc.count = rs ? L.S / esz : L.count;
     if (widened) pc.form.bits = 0;  // accumulate cleared: the region receives the accumulator itself, the unpack adds
-    const ncclResult_t crc = run_plain(pc);
+    const ncclResult_t crc = run_call(pc);  // a ring reduce-scatter or a wide run stages through other buffers
     keep_first(&first, crc);
     g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
     g_group_stats[3].fetch_add(1, std::memory_order_relaxed);
@@ -952,7 +988,7 @@ ncclResult_t run_queue(const std::vector<Call>& q) {
             continue;
         }
         for (size_t i = r.first; i < r.first + r.n; ++i) {
-            keep_first(&first, run_plain(q[i]));
+            keep_first(&first, run_call(q[i]));
             g_group_stats[2].fetch_add(1, std::memory_order_relaxed);
         }
     }
