@@ -119,6 +119,9 @@ def _load():
         "dccl_local_convert_scaled": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p]),
         "dccl_local_reduce_chain_widen": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
                                                   c_size_t, c_int, c_void_p]),
+        "dccl_local_reduce_chain_widen_checked": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int,
+                                                          c_size_t, c_int, c_void_p, c_void_p]),
+        "dccl_local_nonfinite_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
         "dccl_register_host_memory": (c_int, [c_void_p, c_size_t]),
         "dccl_deregister_host_memory": (c_int, [c_void_p]),
         "dccl_size_of_type": (c_size_t, [c_int]),
@@ -147,6 +150,7 @@ def _load():
         "dccl_red_op_create_wide_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_void_p]),
         "dccl_red_op_create_wide_scaled_sum": (c_int, [ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p]),
         "dccl_red_op_create_widened_sum": (c_int, [ctypes.POINTER(c_int), c_int, c_int, c_void_p]),
+        "dccl_red_op_create_widened_sum_checked": (c_int, [ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_void_p]),
         "dccl_rccl_available": (c_int, []),
         "dccl_bootstrap_unique_id": (c_int, [ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
         "dccl_bootstrap_done": (c_int, [ctypes.c_uint32, ctypes.c_uint32]),
@@ -185,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "dccl_local_reduce_chain_wide", "dccl_local_convert", "dccl_red_op_create_wide_sum",
     "dccl_local_reduce_chain_wide_scaled", "dccl_local_convert_scaled", "dccl_red_op_create_wide_scaled_sum",
     "dccl_local_reduce_chain_widen", "dccl_red_op_create_widened_sum", "dccl_add_rows_f32_multi",
+    "dccl_local_reduce_chain_widen_checked", "dccl_local_nonfinite_f32", "dccl_red_op_create_widened_sum_checked",
 ]
 
 #: names of the dccl_ipc_stats counters, in order (include/dccl/dccl_comm.h); registered_hits,
@@ -314,6 +319,23 @@ def local_reduce_chain_widen(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, 
     arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
     return int(lib.dccl_local_reduce_chain_widen(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype), int(count),
                                                  int(accumulate), stream or None))
+
+
+def local_reduce_chain_widen_checked(send_ptrs, own_ptr: int, dst_ptr: int, dtype: int, count: int, accumulate: int,
+                                     flag_ptr: int, stream: int = 0) -> int:
+    """local_reduce_chain_widen with the same bits, which also stores 1 to the device uint32 at ``flag_ptr`` when a
+    finished accumulator (before ``accumulate``'s add) is +-inf or NaN; nothing is stored otherwise, and the word is
+    never read or cleared."""
+    arr = (ctypes.c_void_p * max(1, len(send_ptrs)))(*send_ptrs)
+    return int(lib.dccl_local_reduce_chain_widen_checked(arr, len(send_ptrs), own_ptr, dst_ptr, int(dtype),
+                                                         int(count), int(accumulate), flag_ptr or None,
+                                                         stream or None))
+
+
+def local_nonfinite_f32(src_ptr: int, count: int, flag_ptr: int, stream: int = 0) -> int:
+    """Stores 1 to the device uint32 at ``flag_ptr`` when one of ``count`` float32 at ``src_ptr`` is +-inf or NaN;
+    ``src`` is only read, nothing is stored otherwise."""
+    return int(lib.dccl_local_nonfinite_f32(src_ptr or None, int(count), flag_ptr or None, stream or None))
 
 
 def local_convert_scaled(src_ptr: int, src_dtype: int, dst_ptr: int, dst_dtype: int, count: int, scalar_ptr: int,
@@ -492,6 +514,15 @@ class Comm:
         it."""
         op = ctypes.c_int(-1)
         rc = int(lib.dccl_red_op_create_widened_sum(ctypes.byref(op), int(dtype), int(accumulate), self.handle))
+        return rc, int(op.value)
+
+    def red_op_create_widened_sum_checked(self, dtype: int, accumulate: int, flag_ptr: int):
+        """dcclRedOpCreateWidenedSumChecked: red_op_create_widened_sum whose collectives also store 1 to the device
+        uint32 at ``flag_ptr`` when an element of the float32 sum delivered to this rank is +-inf or NaN (nothing
+        otherwise; zero the word yourself, it stays raised).  Returns (rc, op)."""
+        op = ctypes.c_int(-1)
+        rc = int(lib.dccl_red_op_create_widened_sum_checked(ctypes.byref(op), int(dtype), int(accumulate),
+                                                            flag_ptr or None, self.handle))
         return rc, int(op.value)
 
     def red_op_destroy(self, op: int) -> int:

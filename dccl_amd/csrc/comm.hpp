@@ -98,7 +98,8 @@ private:
 //   kWideScaledSum  dcclRedOpCreateWideScaledSum: the scalar is ONE fp32, times the finished fp32 accumulator
 //   kWidenedSum     dcclRedOpCreateWidenedSum: fp16 / bf16 accumulated in fp32 and NOT rounded: recvbuff holds fp32
 //                   (ncclReduceScatter and ncclReduce only); no scalar; `bits` holds its accumulate flag (0 / 1:
-//                   the sum replaces recvbuff's content, or is added to it by one fp32 add): accumulate()
+//                   the sum replaces recvbuff's content, or is added to it by one fp32 add): accumulate(); its
+//                   checked form (dcclRedOpCreateWidenedSumChecked) keeps the caller's flag word: nonfinite()
 // Readers switch on `kind` or ask the accessor named for their question, never the scalar's storage.  A host-immediate
 // scalar lives in `bits`: a copy of the form (a queued call, a packed run) is complete, and its scalar() valid as long.
 // (SumKind itself is in select.hpp, which has no HIP include.)
@@ -110,6 +111,11 @@ struct SumForm {
     bool has_scalar() const { return kind == kPremulSum || kind == kWideScaledSum; }
     bool widened() const { return kind == kWidenedSum; }  // the output is fp32, whatever the input's dtype
     bool accumulate() const { return kind == kWidenedSum && bits != 0; }
+    // dcclRedOpCreateWidenedSumChecked: the device word the reduction raises when a reduced value is not finite
+    // (DESIGN.md §7.12), else nullptr.  A widened sum has no scalar, so the form's `dev_ptr` carries it.
+    uint32_t* nonfinite() const {
+        return kind == kWidenedSum ? static_cast<uint32_t*>(const_cast<void*>(dev_ptr)) : nullptr;
+    }
     // the C entry points' (scalar, residence) pair
     const void* scalar() const { return dev_ptr != nullptr ? dev_ptr : static_cast<const void*>(&bits); }
     int residence() const { return dev_ptr != nullptr ? dccl::ncclScalarDevice : dccl::ncclScalarHostImmediate; }

@@ -31,6 +31,7 @@
 
 #include "algorithms.hpp"
 #include "bootstrap.hpp"
+#include "checked_entry.hpp"
 #include "comm.hpp"
 #include "direct.hpp"
 #include "group_plan.hpp"
@@ -117,6 +118,12 @@ ncclResult_t stage_input(void* dst, const void* src, size_t count, int dtype, co
 bool ranges_share_a_byte(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y ? y - x < na : x - y < nb;
+}
+
+// A checked widened sum's flag word (comm.hpp SumForm::nonfinite) shares a byte with recvbuff's `count` fp32.
+bool flag_in_recv(const SumForm& form, const void* recv, size_t count) {
+    const uint32_t* flag = form.nonfinite();
+    return flag != nullptr && ranges_share_a_byte(flag, sizeof(uint32_t), recv, count * sizeof(float));
 }
 
 ncclResult_t placement(const void* send, const void* recv, bool* device) {
@@ -535,6 +542,7 @@ ncclResult_t rs_validate(const void* sendbuff, void* recvbuff, size_t recvcount,
     if (c->form.widened() && ranges_share_a_byte(sendbuff, recvcount * comm->world * size_of_dtype(datatype), recvbuff,
                                                  recvcount * sizeof(float)))
         return ncclInvalidArgument;  // recvbuff holds fp32: no in-place form
+    if (flag_in_recv(c->form, recvbuff, recvcount)) return ncclInvalidArgument;
     if ((rc = check_buffers(comm, sendbuff, recvbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduceScatter, comm, sendbuff, recvbuff, recvcount, datatype);
     return ncclSuccess;
@@ -590,6 +598,7 @@ ncclResult_t reduce_validate(const void* sendbuff, void* recvbuff, size_t count,
     if (c->form.widened() && iamroot &&
         ranges_share_a_byte(sendbuff, count * size_of_dtype(datatype), recvbuff, count * sizeof(float)))
         return ncclInvalidArgument;  // the root's recvbuff holds fp32: no in-place form
+    if (iamroot && flag_in_recv(c->form, recvbuff, count)) return ncclInvalidArgument;
     if ((rc = check_buffers(comm, sendbuff, iamroot ? recvbuff : sendbuff, c->form, &c->dev)) != ncclSuccess) return rc;
     set_call(c, group::kReduce, comm, sendbuff, recvbuff, count, datatype);
     c->root = root;
@@ -732,6 +741,9 @@ ncclResult_t run_plain(const Call& c) {
 // that collective writes recvbuff itself (the root's, for ncclReduce: it is the buffer the fp32 ring then runs in).
 // With it the result stays in staging (a reduce-scatter's behind the widened input) and one fp32 Sum combine adds it
 // to recvbuff.  W == 1: the conversion alone, or the conversion into staging and the same add.
+// A checked sum (SumForm::nonfinite): on the ranks that have output, one read-only pass over the
+// fp32 sum this rank received raises the caller's flag, ahead of the accumulate add (the flag reports the
+// contributions, as the direct chain's does).
 ncclResult_t widened_staged(const Call& c) {
     hipStream_t stream = c.stream;
     dcclComm* comm = c.comm;
@@ -739,8 +751,12 @@ ncclResult_t widened_staged(const Call& c) {
     const bool rs = c.api == group::kReduceScatter, acc = c.form.accumulate();
     const size_t in_count = rs ? c.count * W : c.count, out_count = c.count;
     const bool has_out = rs || comm->rank == uint32_t(c.root);
-    if (W == 1 && !acc)
-        return static_cast<ncclResult_t>(dccl_local_convert(c.send, c.dtype, c.recv, ncclFloat32, out_count, stream));
+    uint32_t* const flag = c.form.nonfinite();
+    if (W == 1 && !acc) {
+        const int rc = dccl_local_convert(c.send, c.dtype, c.recv, ncclFloat32, out_count, stream);
+        if (rc != DCCL_SUCCESS || flag == nullptr) return static_cast<ncclResult_t>(rc);
+        return static_cast<ncclResult_t>(dccl_local_nonfinite_f32(c.recv, out_count, flag, stream));
+    }
     ncclResult_t rc = ensure_wide(comm, (in_count + (rs && acc ? out_count : 0)) * sizeof(float));
     if (rc != ncclSuccess) return rc;
     float* wide = static_cast<float*>(comm->dev_wide);
@@ -757,7 +773,9 @@ ncclResult_t widened_staged(const Call& c) {
         rc = run_plain(f);
         sum = static_cast<const float*>(f.recv);
     }
-    if (rc != ncclSuccess || !has_out || !acc) return rc;
+    if (rc != ncclSuccess || !has_out) return rc;
+    if (flag != nullptr) rc = static_cast<ncclResult_t>(dccl_local_nonfinite_f32(sum, out_count, flag, stream));
+    if (rc != ncclSuccess || !acc) return rc;
     return static_cast<ncclResult_t>(dccl_local_reduce(sum, c.recv, ncclFloat32, out_count, ncclSum, stream));
 }
 
@@ -935,6 +953,12 @@ ncclResult_t run_packed(const Call* calls, const group::Call* plan, size_t n) {
     dccl_copy_rows_t segs[group::kMaxRun];
     for (size_t i = 0; i < n; ++i) segs[i] = {calls[i].send, pack + L.off[i], L.slot[i], L.slot[i], L.S};
     keep_first(&first, static_cast<ncclResult_t>(copy_rows_launch(segs, int(n), uint32_t(P), st)));
+    // A checked run: the collective tests every element of the packed slots, the pad bytes at their
+    // ends included, and those hold whatever an earlier, larger run packed there.  This rank zeroes its own pack's
+    // pads (zeros add nothing non-finite); the peers, in the same run, zero theirs.  Unchecked runs never look.
+    if (const size_t used = L.off[n - 1] + L.slot[n - 1]; c0.form.nonfinite() != nullptr && used < L.S)
+        for (size_t k = 0; k < P; ++k)
+            keep_first(&first, hip_rc(hipMemsetAsync(pack + k * L.S + used, 0, L.S - used, st)));
     Call pc = c0;
     pc.send = pack;
     pc.recv = pack + out_at;
@@ -1088,6 +1112,23 @@ ncclResult_t dcclRedOpCreateWidenedSum(ncclRedOp_t* op, ncclDataType_t datatype,
     // no scalar: the form's `bits` carry the flag (comm.hpp SumForm::accumulate)
     const uint64_t flag = uint64_t(accumulate);
     return create_user_op(comm, kWidenedSum, datatype, &flag, ncclScalarHostImmediate, sizeof(flag), op);
+}
+
+ncclResult_t dcclRedOpCreateWidenedSumChecked(ncclRedOp_t* op, ncclDataType_t datatype, int accumulate,
+                                              uint32_t* nonfinite, ncclComm_t comm) {
+    validate_comm(comm, __func__);
+    if (op == nullptr) return ncclInvalidArgument;
+    if (datatype != ncclFloat16 && datatype != ncclBfloat16) return ncclInvalidArgument;
+    if (accumulate != 0 && accumulate != 1) return ncclInvalidArgument;
+    if (nonfinite == nullptr || reinterpret_cast<uintptr_t>(nonfinite) % sizeof(uint32_t)) return ncclInvalidArgument;
+    if (!checked_entries_linked()) return ncclInternalError;  // a build without wide.hip's checked entry points
+    ncclRedOp_t h;
+    const uint64_t acc = uint64_t(accumulate);
+    const ncclResult_t rc = create_user_op(comm, kWidenedSum, datatype, &acc, ncclScalarHostImmediate, sizeof(acc), &h);
+    if (rc != ncclSuccess) return rc;
+    comm->user_ops[int(h) - int(ncclNumOps)].form.dev_ptr = nonfinite;  // SumForm::nonfinite()
+    *op = h;
+    return ncclSuccess;
 }
 
 ncclResult_t ncclRedOpDestroy(ncclRedOp_t op, ncclComm_t comm) {
@@ -1282,6 +1323,14 @@ extern "C" int dccl_red_op_create_widened_sum(int* op, int dtype, int accumulate
     return create_handle(op, [&](dccl::ncclRedOp_t* h) {
         return dccl::dcclRedOpCreateWidenedSum(h, static_cast<dccl::ncclDataType_t>(dtype), accumulate,
                                                static_cast<dccl::ncclComm_t>(comm));
+    });
+}
+
+extern "C" int dccl_red_op_create_widened_sum_checked(int* op, int dtype, int accumulate, void* flag, void* comm) {
+    return create_handle(op, [&](dccl::ncclRedOp_t* h) {
+        return dccl::dcclRedOpCreateWidenedSumChecked(h, static_cast<dccl::ncclDataType_t>(dtype), accumulate,
+                                                      static_cast<uint32_t*>(flag),
+                                                      static_cast<dccl::ncclComm_t>(comm));
     });
 }
 

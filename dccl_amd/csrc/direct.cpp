@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "bootstrap.hpp"
+#include "checked_entry.hpp"
 #include "dccl/dccl_reduce.h"
 #include "dispatch.hpp"
 #include "ipc_cache.hpp"
@@ -644,7 +645,10 @@ ncclResult_t chain(const Peers& P, uint32_t W, uint32_t first, size_t off, const
         rc = dccl_local_reduce_chain_wide_scaled(sends, k, own, dst, dtype, elems, form.scalar(), form.residence(), s);
         break;
     case kWidenedSum:  // that accumulator stored as fp32 (dst holds fp32), or added to what dst holds
-        rc = dccl_local_reduce_chain_widen(sends, k, own, dst, dtype, elems, form.accumulate() ? 1 : 0, s);
+        if (uint32_t* flag = form.nonfinite())  // the checked form: the same launch raises the caller's flag
+            rc = dccl_local_reduce_chain_widen_checked(sends, k, own, dst, dtype, elems, form.accumulate() ? 1 : 0,
+                                                       flag, s);
+        else rc = dccl_local_reduce_chain_widen(sends, k, own, dst, dtype, elems, form.accumulate() ? 1 : 0, s);
         break;
     }
     return static_cast<ncclResult_t>(rc);

@@ -6,6 +6,8 @@
 //                                         acc = widen(own[i]) + acc;  dst[i] = round16(acc)
 //   dccl_local_reduce_chain_wide_scaled   the same acc;  dst[i] = round16(acc * s)
 //   dccl_local_reduce_chain_widen         the same acc;  dst (fp32)[i] = acc, or dst[i] + acc
+//   dccl_local_reduce_chain_widen_checked the same, and *flag = 1 when some acc is +-inf or NaN
+//   dccl_local_nonfinite_f32              *flag = 1 when some src (fp32)[i] is +-inf or NaN; reads only
 //   dccl_local_convert                    dst[i] = widen(src[i]) (fp16 / bf16 -> fp32, exact) or round16(src[i])
 //                                         (fp32 -> fp16 / bf16, nearest-even)
 //   dccl_local_convert_scaled             dst[i] = round16(as_fp32(src[i]) * s), src fp32 or dst's own 16-bit type
@@ -180,11 +182,31 @@ __global__ __launch_bounds__(kBlock) void wide_scaled_chain_elem_kernel(SendList
 // A sibling of chain_vec_body, whose loads, order and edge elements it follows: the 16-bit operands are walked in
 // 16-B vectors, dst in the 2 x 16 B that hold the same eight elements (convert_vec_kernel<T, true>'s stores).
 // `head` elements bring the 16-bit operands to their 16-B boundary; dst is on one there too (widen_typed). ----
-template <typename T, int K, bool ACC, typename C>
+//
+// CHECK (dccl_local_reduce_chain_widen_checked): every finished accumulator, before ACC's add, passes
+// an integer test of its exponent field, ORed into one register of the thread over all of its tiles and edge
+// elements; a thread that saw a non-finite one stores 1 to `flag` after its loops.  Every writer stores the same
+// word, so there is no atomic, no LDS and no cross-lane step, and nothing is stored when every accumulator is finite.
+
+// Bit 31 of the result is set exactly when acc's exponent field is all ones (+-inf or a NaN): the field plus one
+// carries into it, any other field does not.  Integer arithmetic on the bits: nothing a float comparison could fold.
+__device__ __forceinline__ uint32_t nonfinite_bit(float acc) {
+    return (__builtin_bit_cast(uint32_t, acc) & 0x7f800000u) + 0x00800000u;
+}
+__device__ __forceinline__ void raise_if(uint32_t bad, uint32_t* flag) {
+    if (bad >> 31) *flag = 1u;
+}
+// The kernels' last argument: the flag's address, or nothing at all for the unchecked instances, whose code is the
+// one they had before CHECK existed ("Build facts").
+template <bool CHECK> struct FlagArg { uint32_t* p; };
+template <> struct FlagArg<false> {};
+
+template <typename T, int K, bool ACC, typename C, bool CHECK = false>
 __global__ __launch_bounds__(C::BLOCK) void widen_chain_vec_kernel(SendList sends, const unsigned char* own,
                                                                    unsigned char* dst, size_t head, size_t nvec,
-                                                                   size_t tail) {
+                                                                   size_t tail, FlagArg<CHECK> flag) {
     static_assert(C::UNROLL == 1, "one vector per lane");
+    [[maybe_unused]] uint32_t bad = 0;
     const size_t off = head * sizeof(T);
     const u32x4* vo = reinterpret_cast<const u32x4*>(own + off);
     u32x4* vd = reinterpret_cast<u32x4*>(dst + head * sizeof(float));
@@ -204,6 +226,16 @@ __global__ __launch_bounds__(C::BLOCK) void widen_chain_vec_kernel(SendList send
 #pragma unroll
             for (int k = 1; k < K; ++k) acc = add16<T>(s[k], acc);
             acc = add16<T>(o, acc);
+            if constexpr (CHECK) {
+#pragma unroll
+                for (int l = 0; l < kLanes16; ++l) bad |= nonfinite_bit(acc.f[l]);
+                // ACC false: the test ends here.  Left to itself the scheduler puts it between the two stores below,
+                // the two halves of each lane's 32 B, and this kernel, which only writes dst, then ran 10 % (k = 3)
+                // to 33 % (k = 1) longer at 32 Mi elements than its unchecked twin, whose stores are back to back
+                // (DESIGN.md §7.12 "The scheduling barrier"; both runs: profiles/widen_checked_ab.json).  With ACC
+                // the scheduler's own order measured equal, and stays.
+                if constexpr (!ACC) __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (ACC) {
                 const F32x8 was = __builtin_bit_cast(F32x8, prior);
 #pragma unroll
@@ -221,24 +253,50 @@ __global__ __launch_bounds__(C::BLOCK) void widen_chain_vec_kernel(SendList send
 #pragma unroll
             for (int k = 1; k < K; ++k) acc = Wide<T>::widen(ld_elem<T, true>(sends.p[k], i)) + acc;
             acc = Wide<T>::widen(ld_elem<T, true>(own, i)) + acc;
+            if constexpr (CHECK) bad |= nonfinite_bit(acc);
             if constexpr (ACC) acc = ld_elem<float, true>(dst, i) + acc;
             st_elem<float, true>(dst, i, acc);
         }
     }
+    if constexpr (CHECK) raise_if(bad, flag.p);
 }
 
 // Any placement, one element per thread and step (correctness only).  ALIGNED: the 16-bit operands on 2-byte and
 // dst on 4-byte boundaries; else byte loads and stores on every side.
-template <typename T, bool ACC, bool ALIGNED>
+template <typename T, bool ACC, bool ALIGNED, bool CHECK = false>
 __global__ __launch_bounds__(kBlock) void widen_chain_elem_kernel(SendList sends, int nsend, const unsigned char* own,
-                                                                  unsigned char* dst, size_t count) {
+                                                                  unsigned char* dst, size_t count,
+                                                                  FlagArg<CHECK> flag) {
+    [[maybe_unused]] uint32_t bad = 0;
     for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < count; i += size_t(gridDim.x) * kBlock) {
         float acc = Wide<T>::widen(ld_elem<T, ALIGNED>(sends.p[0], i));
         for (int k = 1; k < nsend; ++k) acc = Wide<T>::widen(ld_elem<T, ALIGNED>(sends.p[k], i)) + acc;
         acc = Wide<T>::widen(ld_elem<T, ALIGNED>(own, i)) + acc;
+        if constexpr (CHECK) bad |= nonfinite_bit(acc);
         if constexpr (ACC) acc = ld_elem<float, ALIGNED>(dst, i) + acc;
         st_elem<float, ALIGNED>(dst, i, acc);
     }
+    if constexpr (CHECK) raise_if(bad, flag.p);
+}
+
+// ---- dccl_local_nonfinite_f32: the same flag from a read-only pass over fp32 (the staged routes' sums).  One-wave
+// blocks, 16-B non-temporal loads of the aligned body, at most three head and three tail elements in block 0. ----
+__global__ __launch_bounds__(64) void nonfinite_f32_kernel(const unsigned char* src, size_t head, size_t nvec,
+                                                           size_t tail, uint32_t* flag) {
+    const u32x4* vs = reinterpret_cast<const u32x4*>(src + head * sizeof(float));
+    const size_t ntiles = (nvec + 63) / 64;
+    uint32_t bad = 0;
+    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const size_t i = t * 64 + threadIdx.x;
+        if (i >= nvec) continue;
+        const u32x4 v = ld16<true>(vs + i);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) bad |= (v[l] & 0x7f800000u) + 0x00800000u;
+    }
+    if (blockIdx.x == 0)
+        for (size_t j = threadIdx.x; j < head + tail; j += blockDim.x)
+            bad |= nonfinite_bit(ld_elem<float, true>(src, edge_index<float>(j, head, nvec)));
+    raise_if(bad, flag);
 }
 
 // ---- convert: `half` is the 16-bit side, `full` the fp32 side; WIDEN: half -> full, else full -> half ----
@@ -381,8 +439,11 @@ int convert_scaled_typed(const void* src, void* dst, size_t count, ScalarArg sa,
 // launches like launch_chain_form, under the plain chain's caps selected by the fp32 bytes written, which nobody
 // has measured for this kernel (more registers per lane, 4 or 8 more bytes per element on the destination side).
 // Any other placement takes the element-wise kernel: correctness only, nobody has tuned it.
-template <typename T, bool ACC>
-int widen_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count, hipStream_t stream) {
+// CHECK: the kernels' checked instances, with `flag` as their last argument; the rule, the launch and the caps are
+// the same.
+template <typename T, bool ACC, bool CHECK = false>
+int widen_typed(const void* const* sends, int nsend, const void* own, void* dst, size_t count, hipStream_t stream,
+                FlagArg<CHECK> flag = {}) {
     const uintptr_t ao = reinterpret_cast<uintptr_t>(own), ad = reinterpret_cast<uintptr_t>(dst);
     bool elem_ok = ao % sizeof(T) == 0 && ad % sizeof(float) == 0, in_phase = true;
     for (int k = 0; k < nsend; ++k) {
@@ -396,15 +457,15 @@ int widen_typed(const void* const* sends, int nsend, const void* own, void* dst,
     PassPlacement p{false, false, {0, 0, 0}};
     if (elem_ok && in_phase) p = place_pass(ao, sizeof(T), ad, sizeof(float), count);
     if (!p.vec_ok) {
-        void* args[] = {&sl, &nsend, &o, &d, &count};
-        const void* fn = elem_ok ? reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, true>)
-                                 : reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, false>);
+        void* args[] = {&sl, &nsend, &o, &d, &count, &flag};
+        const void* fn = elem_ok ? reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, true, CHECK>)
+                                 : reinterpret_cast<const void*>(&widen_chain_elem_kernel<T, ACC, false, CHECK>);
         return launch(fn, ceil_div(count, size_t(kBlock)), args, stream, kBlock);
     }
     Split& sp = p.sp;
-    void* args[] = {&sl, &o, &d, &sp.head, &sp.nvec, &sp.tail};
+    void* args[] = {&sl, &o, &d, &sp.head, &sp.nvec, &sp.tail, &flag};
     return with_k<1, 8>(nsend, [&](auto K) {
-        return launch(reinterpret_cast<const void*>(&widen_chain_vec_kernel<T, K.value, ACC, DefaultCfg>),
+        return launch(reinterpret_cast<const void*>(&widen_chain_vec_kernel<T, K.value, ACC, DefaultCfg, CHECK>),
                       grid_for(sp, DefaultCfg::TILE), args, stream, DefaultCfg::BLOCK,
                       caps::lds(caps::kChain, K.value, caps_bytes(count * sizeof(float))));
     });
@@ -416,6 +477,32 @@ bool is_16bit_float(int dtype) { return dtype == kFloat16 || dtype == kBfloat16;
 bool ranges_intersect(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y ? y - x < na : x - y < nb;
+}
+
+// a non-finite flag: one uint32_t on its 4-byte boundary
+bool flag_ok(const uint32_t* flag) { return flag != nullptr && reinterpret_cast<uintptr_t>(flag) % 4 == 0; }
+
+// The validation rows dccl_local_reduce_chain_widen and its checked form share, in their order; `flag` is looked at
+// only when `checked`.  *run: validation passed and there is something to launch.
+int check_widen_args(const void* const* sends, int nsend, const void* own, const void* dst, int dtype, size_t count,
+                     int accumulate, bool checked, const uint32_t* flag, bool* run) {
+    *run = false;
+    if (!is_16bit_float(dtype)) return DCCL_INVALID_ARGUMENT;
+    if (accumulate != 0 && accumulate != 1) return DCCL_INVALID_ARGUMENT;
+    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
+    if (checked && !flag_ok(flag)) return DCCL_INVALID_ARGUMENT;
+    if (count == 0) return DCCL_SUCCESS;
+    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
+    for (int k = 0; k < nsend; ++k)
+        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
+    // no shared byte with the fp32 destination (dccl_local_convert's rule: the element sizes differ)
+    const size_t in_bytes = count * size_of_dtype(dtype), out_bytes = count * sizeof(float);
+    for (int k = 0; k < nsend; ++k)
+        if (ranges_intersect(sends[k], in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    if (ranges_intersect(own, in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    if (checked && ranges_intersect(flag, sizeof(uint32_t), dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    *run = true;
+    return DCCL_SUCCESS;
 }
 
 }  // namespace
@@ -435,24 +522,41 @@ extern "C" int dccl_local_reduce_chain_wide(const void* const* sends, int nsend,
 
 extern "C" int dccl_local_reduce_chain_widen(const void* const* sends, int nsend, const void* own, void* dst,
                                              int dtype, size_t count, int accumulate, void* stream) {
-    if (!is_16bit_float(dtype)) return DCCL_INVALID_ARGUMENT;
-    if (accumulate != 0 && accumulate != 1) return DCCL_INVALID_ARGUMENT;
-    if (nsend < 1 || nsend > 8 || sends == nullptr) return DCCL_INVALID_ARGUMENT;
-    if (count == 0) return DCCL_SUCCESS;
-    if (own == nullptr || dst == nullptr) return DCCL_INVALID_ARGUMENT;
-    for (int k = 0; k < nsend; ++k)
-        if (sends[k] == nullptr) return DCCL_INVALID_ARGUMENT;
-    // no shared byte with the fp32 destination (dccl_local_convert's rule: the element sizes differ)
-    const size_t in_bytes = count * size_of_dtype(dtype), out_bytes = count * sizeof(float);
-    for (int k = 0; k < nsend; ++k)
-        if (ranges_intersect(sends[k], in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
-    if (ranges_intersect(own, in_bytes, dst, out_bytes)) return DCCL_INVALID_ARGUMENT;
+    bool run;
+    const int rc = check_widen_args(sends, nsend, own, dst, dtype, count, accumulate, false, nullptr, &run);
+    if (!run) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype == kFloat16)
         return accumulate ? widen_typed<f16_bits, true>(sends, nsend, own, dst, count, st)
                           : widen_typed<f16_bits, false>(sends, nsend, own, dst, count, st);
     return accumulate ? widen_typed<bf16_bits, true>(sends, nsend, own, dst, count, st)
                       : widen_typed<bf16_bits, false>(sends, nsend, own, dst, count, st);
+}
+
+extern "C" int dccl_local_reduce_chain_widen_checked(const void* const* sends, int nsend, const void* own, void* dst,
+                                                     int dtype, size_t count, int accumulate, uint32_t* flag,
+                                                     void* stream) {
+    bool run;
+    const int rc = check_widen_args(sends, nsend, own, dst, dtype, count, accumulate, true, flag, &run);
+    if (!run) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == kFloat16)
+        return accumulate ? widen_typed<f16_bits, true, true>(sends, nsend, own, dst, count, st, {flag})
+                          : widen_typed<f16_bits, false, true>(sends, nsend, own, dst, count, st, {flag});
+    return accumulate ? widen_typed<bf16_bits, true, true>(sends, nsend, own, dst, count, st, {flag})
+                      : widen_typed<bf16_bits, false, true>(sends, nsend, own, dst, count, st, {flag});
+}
+
+extern "C" int dccl_local_nonfinite_f32(const void* src, size_t count, uint32_t* flag, void* stream) {
+    if (!flag_ok(flag)) return DCCL_INVALID_ARGUMENT;
+    if (count == 0) return DCCL_SUCCESS;
+    if (src == nullptr || reinterpret_cast<uintptr_t>(src) % sizeof(float)) return DCCL_INVALID_ARGUMENT;
+    if (ranges_intersect(flag, sizeof(uint32_t), src, count * sizeof(float))) return DCCL_INVALID_ARGUMENT;
+    auto s = static_cast<const unsigned char*>(src);
+    Split sp = split_for_vectors(reinterpret_cast<uintptr_t>(src), count, sizeof(float), 16);
+    void* args[] = {&s, &sp.head, &sp.nvec, &sp.tail, &flag};
+    return launch(reinterpret_cast<const void*>(&nonfinite_f32_kernel), grid_for(sp, 64), args,
+                  static_cast<hipStream_t>(stream), 64);
 }
 
 extern "C" int dccl_local_convert(const void* src, int src_dtype, void* dst, int dst_dtype, size_t count,

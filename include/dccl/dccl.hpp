@@ -154,6 +154,32 @@ ncclResult_t dcclRedOpCreateWideScaledSum(ncclRedOp_t* op, const void* scalar, n
  *  1/W itself. */
 ncclResult_t dcclRedOpCreateWidenedSum(ncclRedOp_t* op, ncclDataType_t datatype, int accumulate, ncclComm_t comm);
 
+/** Checked widened sum: the widened sum above, whose reduction also answers "did any reduced gradient come out inf or
+ *  NaN?" (the question a loss scaler asks before the optimizer step) without a second pass over the fp32 shard.
+ *  `nonfinite` is one uint32_t in device memory of the calling rank's device, on a 4-byte boundary.  The library
+ *  stores the value 1 to it when at least one element of the fp32 Sum collective's result DELIVERED TO THIS RANK is
+ *  not finite (fp32 exponent field all ones: +inf, -inf or any NaN), and stores nothing otherwise.  It never reads
+ *  the word, never clears it and never stores another value: the caller zeroes it, and it stays raised over as many
+ *  calls (and ops, and streams) as the caller likes.  The store is ordered on the collective's stream like
+ *  `recvbuff`'s.  ncclReduceScatter: each rank's flag covers its own shard (all-reduce the flags for a global
+ *  answer).  ncclReduce: only the root's flag can be raised; the other ranks' flags are never written.
+ *  The flag reports the contributions, not the caller's running buffer: with `accumulate` == 1 the previous content
+ *  of `recvbuff` does not enter the test (a `recvbuff` that already holds inf leaves the flag alone when the
+ *  contributions are finite), and a finite previous value plus a finite sum that overflows in that last add does
+ *  NOT raise it.  The reduced values are exactly the unchecked widened sum's bits, on every path.  Every rank of the
+ *  communicator creates the op as a checked one (each with its own flag), as every rank passes the same op to a
+ *  collective.  The direct collectives test the accumulators their chain launch already holds; every other path
+ *  reads this rank's fp32 result once more before it is delivered; coalesced groups (same handle) keep coalescing
+ *  and additionally clear the pad bytes of their packed slots.  Errors: dcclRedOpCreateWidenedSum's, and a NULL or
+ *  misaligned `nonfinite`: ncclInvalidArgument.  At the collective: the widened sum's, and the flag's 4 bytes sharing
+ *  a byte with `recvbuff`'s fp32 range (on a rank that has output): ncclInvalidArgument.  The flag must not lie
+ *  inside `sendbuff` either (not checked).  A coalesced run of same-handle calls takes the flag, like `accumulate`,
+ *  from the run's first call: an op destroyed and another created in its slot between two calls of one group makes
+ *  them one run with the first call's flag.  There is no checked
+ *  all-reduce, and no flag for the wide or scaled wide sums. */
+ncclResult_t dcclRedOpCreateWidenedSumChecked(ncclRedOp_t* op, ncclDataType_t datatype, int accumulate,
+                                              uint32_t* nonfinite, ncclComm_t comm);
+
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);
 ncclResult_t ncclReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount,

@@ -122,6 +122,16 @@
  *                         limit is on the 16-bit payload; an accumulate handle's run is unpacked by
  *                         dccl_add_rows_f32_multi); calls with different handles, or a widened and a plain or wide
  *                         call, never share a run.
+ *   dccl_red_op_create_widened_sum_checked  dcclRedOpCreateWidenedSumChecked: the widened sum, which also stores 1 to
+ *                         `flag` (one uint32_t of device memory on a 4-byte boundary) when an element of the fp32
+ *                         sum delivered to this rank is +-inf or a NaN, and nothing otherwise.  The library never
+ *                         reads, clears or otherwise writes the word: zero it, and it stays raised over as many
+ *                         calls as you like.  dccl_reduce_scatter: each rank's flag covers its shard; dccl_reduce:
+ *                         only the root's flag can be raised.  The previous content of recv (accumulate 1) does not
+ *                         enter the test, and finite + finite overflowing in that last add does not raise the flag.
+ *                         The values are the unchecked op's bits.  Create: dccl_red_op_create_widened_sum's rows,
+ *                         and a NULL or misaligned flag -> 4.  At the collective: its rows, and the flag's 4 bytes
+ *                         sharing a byte with recv's fp32 range -> 4.  Same-handle calls in a group still coalesce.
  * A null / finalized communicator returns ncclInvalidArgument (4) instead of throwing.
  */
 #ifndef DCCL_COMM_H_
@@ -155,6 +165,7 @@ int dccl_red_op_destroy(int op, void* comm);
 int dccl_red_op_create_wide_sum(int* op, int dtype, void* comm);
 int dccl_red_op_create_wide_scaled_sum(int* op, const void* scalar, int dtype, int residence, void* comm);
 int dccl_red_op_create_widened_sum(int* op, int dtype, int accumulate, void* comm);
+int dccl_red_op_create_widened_sum_checked(int* op, int dtype, int accumulate, void* flag, void* comm);
 int dccl_rccl_available(void);
 int dccl_comm_register(void* comm, void* buffer, size_t size);
 int dccl_comm_deregister(void* comm, void* buffer);

@@ -178,6 +178,35 @@ int dccl_local_reduce_chain_widen(const void* const* sends, int nsend, const voi
                                   size_t count, int accumulate, void* stream);
 
 /*
+ * Checked widened sum (the device half of dcclRedOpCreateWidenedSumChecked): the widened sum above, which also tells
+ * whether a reduced value came out non-finite, from the registers the chain already holds.
+ *   dccl_local_reduce_chain_widen_checked  dccl_local_reduce_chain_widen, bit for bit (the check changes no stored
+ *                                   value), and: when acc of at least one element i is not finite (fp32 exponent
+ *                                   field all ones: +inf, -inf or any NaN), the value 1 is stored to *flag.  acc is
+ *                                   the accumulator after widen(own[i]) + acc, BEFORE accumulate's add.
+ *   dccl_local_nonfinite_f32        the same rule over `count` fp32 at src, which is only read: *flag = 1 when some
+ *                                   src[i] is +-inf or a NaN.  It serves the staged collectives, and any caller.
+ * `flag` is one uint32_t in device memory, on a 4-byte boundary.  Nothing else is ever stored to it: it is not read,
+ * not cleared and never given another value, so the caller zeroes it and it stays raised over as many calls as the
+ * caller likes (several calls may share one flag, on one stream or many).  When every acc is finite nothing is
+ * stored.  The flag reports the CONTRIBUTIONS, not the caller's running buffer: with accumulate == 1 the previous
+ * content of dst does not enter the test (a dst that already holds inf, with finite contributions, leaves the flag
+ * alone), and a finite dst[i] + finite acc that overflows in that last add does NOT raise it.  The store is ordered
+ * on `stream` like dst's.  The flag must not lie inside sends[j] or own either: that is the caller's to see to (no
+ * validation row; a kernel would store to a word that other lanes read as an operand).
+ * Validation of dccl_local_reduce_chain_widen_checked: dccl_local_reduce_chain_widen's rows in their order, with two
+ * more: directly after the nsend / sends row (so ahead of count == 0), NULL flag or flag off its 4-byte boundary 4;
+ * after the operand-overlap rows, [flag, flag + 4) sharing a byte with [dst, dst + 4 count) 4.  count == 0 succeeds
+ * and touches nothing.  Same placement rule, kernels' shape, launch and caps as dccl_local_reduce_chain_widen.
+ * Validation of dccl_local_nonfinite_f32, in this order: NULL or misaligned flag 4; count == 0 succeeds; NULL src or
+ * src off its 4-byte boundary 4; flag inside [src, src + 4 count) 4; launch failure 1.  One-wave blocks read the
+ * 16-byte-aligned body in 16-byte vectors; at most three head and three tail elements are read one by one.
+ */
+int dccl_local_reduce_chain_widen_checked(const void* const* sends, int nsend, const void* own, void* dst, int dtype,
+                                          size_t count, int accumulate, uint32_t* flag, void* stream);
+int dccl_local_nonfinite_f32(const void* src, size_t count, uint32_t* flag, void* stream);
+
+/*
  * Multi-source device copy: dsts[y][0..bytes) = srcs[y][0..bytes) for y < npairs (<= 8), in one
  * launch, so the reads of several peers' chunks use several xGMI links at once (the all-gather
  * half of the direct collectives; replaces W-1 ring all-gather steps,
